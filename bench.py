@@ -2,7 +2,7 @@
 """Headline benchmark: image-pairs/sec, forward only, yolov5l + CFTx3 (FLIR cfg), 640x640, batch 64
 per GPU, bf16 compute (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -90,6 +90,30 @@ def gemm_family_time(model, rgb, ir):
     flops = sum(v[1] for v in fam.values())
     secs = sum(v[2] for v in fam.values())
     return n, flops, secs, fam, ovh, abytes, aux
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, pred, raw, seed=0):
+    """--dump-outputs: ``pred`` and the three ``raw`` maps of one step as float32 ``out_dir/<name>.npy``.  When the whole batch
+    exceeds DUMP_BUDGET_BYTES, the same rows (image pairs) of every array are kept: a fixed subset drawn by a seeded generator,
+    so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    arrays = {"pred": pred, **{f"raw{i}": r for i, r in enumerate(raw)}}
+    batch = pred.shape[0]
+    row_bytes = sum(t[0].numel() * 4 for t in arrays.values())
+    k = min(batch, DUMP_BUDGET_BYTES // row_bytes)
+    if k < 1:
+        raise SystemExit(f"--dump-outputs: one image pair's outputs ({row_bytes / 1e6:.1f} MB) exceed {DUMP_BUDGET_BYTES / 1e6:.0f} MB")
+    rows = torch.arange(batch) if k == batch else torch.randperm(batch, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t[rows.to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "rows": rows.tolist(), "shapes": shapes}
 
 
 def log(msg):
@@ -376,6 +400,8 @@ def main():
                     "(Infinity-Cache residency); empty = layer by layer over the whole batch")
     ap.add_argument("--stream-priorities", default="", help="A/B: HIP stream priority per forward in flight, e.g. -1,0 (ForwardPipeline.pick_streams(priorities=...); "
                     "round 4 measured (-1, 0) and (-1, -1) slower than equal priorities, profiles/r04_forwards_in_flight.txt)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the outputs of the last timed step (pred, raw0..2) "
+                    "as float32 DIR/<name>.npy; batches larger than 64 MB are sampled by a fixed, seeded subset of pairs (the rows are listed in the line)")
     ap.add_argument("--conv-variant", type=int, default=0, help="A/B runs: cft_set_conv_variant() for the whole process (0 = automatic)")
     args = ap.parse_args()
 
@@ -422,7 +448,11 @@ def main():
     fly_single = False
     with torch.no_grad():
         if args.no_graph:
-            step_seq = lambda: model.forward_once(rgb, ir)   # noqa: E731
+            eager_out = []
+
+            def step_seq():
+                eager_out[:] = model.forward_once(rgb, ir)
+                return eager_out
             caps = []
         else:
             from msod_amd.graph import CapturedForward
@@ -467,6 +497,15 @@ def main():
     assert torch.isfinite(pred).all(), "non-finite detections"
     assert all(torch.equal(c.pred, pred) for c in caps[1:]), "the graphs in flight disagree"
     log(f"timed region: {elapsed:.3f} s for {args.steps} steps ({k_fly} in flight)")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if args.no_graph:
+            last_pred, last_raw = eager_out
+        else:       # step t of the pipeline replayed graph t % K: the buffers of the last timed step's graph
+            last = fly_caps[(pipe.tick - 1) % k_fly] if k_fly > 1 else caps[0]
+            last_pred, last_raw = last.pred, last.raw
+        dumped = dump_outputs(args.dump_outputs, last_pred, last_raw)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped['shapes']}")
     local_elapsed = getattr(D.timed_steps, "last_local_elapsed", elapsed)
     n_par = 0 if args.no_parity else min(args.batch, 8)     # the first 8 pairs of the timed batch, at every N (N > 1 lines checked 2)
     with torch.no_grad():
@@ -578,6 +617,7 @@ def main():
                        **({"stream_group_probe_ms_per_step": stream_probe_ms} if stream_probe_ms else {}),
                        **({"depth_first": args.depth_first} if args.depth_first else {}), **({"stream_priorities": args.stream_priorities} if args.stream_priorities else {}),
                        **({"conv_variant": args.conv_variant} if args.conv_variant else {})},
+            **({"dump_outputs": dumped} if dumped else {}),
             "sustained": sustained, "single_in_flight": single, "multi_gpu_selfcheck": selfcheck,
             "roofline": {"bound": "mfma", "kernel": "conv_gemm_kernel (implicit-GEMM conv/linear family; incl. the dedicated Focus kernel and the fused 64- / 128-channel Bottleneck kernels: 2 + 27 launches of the cfg3 forward)",
                          "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),

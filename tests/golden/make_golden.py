@@ -12,6 +12,7 @@ The cases cover: every fusion layout, s and l sizes, nc in {1,3,9}, square and r
 inputs, batch > 1, BN-unfused and ``.fuse()``d forwards, and the derived BASELINE configs.
 """
 import hashlib
+import json
 import logging
 import os
 import sys
@@ -144,6 +145,42 @@ def make_checkpoint():
     torch.save({"cfg": cfg, "seed": 9, "batch": 2, "height": 96, "width": 128, "pred": pred.clone(), "raw": [r.clone() for r in raw],
                 "names": loaded.names, "stride": loaded.stride.clone()}, os.path.join(HERE, "ref_ckpt_tiny_out.pt"))
     print(f"ref_ckpt_tiny.pt {os.path.getsize(path)/1e3:.0f} kB, pred {tuple(pred.shape)}, raw std {raw[0].std():.3f}")
+
+
+def _config_sha256(d):
+    """sha256 of a model config dict (key order ignored); tests/test_host_logic.py hashes the same way."""
+    return hashlib.sha256(json.dumps(d, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
+def _norm_config(d):
+    """The reference yamls write Upsample's size as the string 'None'; named_config() holds None (tests/test_host_logic.py _norm)."""
+    d = dict(d)
+    for part in ("backbone", "head"):
+        d[part] = [[f, n, m, [None if a == "None" else a for a in args]] for f, n, m, args in d[part]]
+    return d
+
+
+def make_config_golden():
+    """``reference_configs.json``: for every reference model yaml, the sha256 of its parsed dict as ``yaml.safe_load`` returns
+    it and of the same dict with 'None' read as None (what ``configs.named_config`` must equal); and the state-dict layout
+    (key, shape) of the reference's own Model built from yolov5s_fusion_transformerx3_vedai.yaml.  Hashes, not the files:
+    the repository stores no reference sources."""
+    import yaml
+    install_reference()
+    sys.path.insert(0, ROOT)
+    import msod_amd  # noqa: F401
+    from msod_amd.models import configs
+    from models.yolo_test import Model  # the reference
+    out = {"yaml_sha256": {}}
+    for name in sorted(configs.REFERENCE_YAMLS):
+        with open(os.path.join(REF, "models", "transformer", name + ".yaml")) as fh:
+            d = yaml.safe_load(fh)
+        out["yaml_sha256"][name] = {"parsed": _config_sha256(d), "normalised": _config_sha256(_norm_config(d))}
+    m = Model(os.path.join(REF, "models", "transformer", "yolov5s_fusion_transformerx3_vedai.yaml"))
+    out["state_dict_layout_yolov5s_fusion_transformerx3_vedai"] = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    with open(os.path.join(HERE, "reference_configs.json"), "w") as fh:
+        json.dump(out, fh, indent=0)
+        fh.write("\n")
 
 
 def make_train_golden():
@@ -365,6 +402,7 @@ if __name__ == "__main__":
         make_lowp_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "survey":
         make_survey_golden()
+        make_config_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "letterbox":
         make_letterbox_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "train":
@@ -373,6 +411,8 @@ if __name__ == "__main__":
         make_nms_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "ckpt":
         make_checkpoint()
+    elif len(sys.argv) > 1 and sys.argv[1] == "configs":
+        make_config_golden()
     else:
         main()
         make_nms_golden()
@@ -381,3 +421,4 @@ if __name__ == "__main__":
         make_letterbox_golden()
         make_lowp_golden()
         make_survey_golden()
+        make_config_golden()

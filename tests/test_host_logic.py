@@ -13,7 +13,6 @@ from msod_amd import _lib, ops
 from msod_amd.models import configs
 from msod_amd.models.yolo_test import Model
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -24,18 +23,37 @@ def _norm(d):
     return d
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
+def _reference_configs():
+    """tests/golden/reference_configs.json (make_golden.py `configs`): hashes of the reference's model yamls as parsed, and the
+    state-dict layout of the reference's own Model built from one of them."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_configs.json")) as fh:
+        return json.load(fh)
+
+
+def _config_sha256(d):
+    import hashlib
+    import json
+    return hashlib.sha256(json.dumps(d, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
+
+
 @pytest.mark.parametrize("name", sorted(configs.REFERENCE_YAMLS))
 def test_generated_config_equals_reference_yaml(name):
+    assert _config_sha256(_norm(configs.named_config(name))) == _reference_configs()["yaml_sha256"][name]["normalised"]
+
+
+def test_reference_yaml_file_builds_unchanged(tmp_path):
+    """A yaml file whose parsed content is exactly the reference's (hash recorded from the reference file; Upsample's size
+    written as the string 'None', as there) builds the network."""
     import yaml
-    with open(f"{REF}/models/transformer/{name}.yaml") as fh:
-        ref = _norm(yaml.safe_load(fh))
-    assert configs.named_config(name) == ref
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_reference_yaml_file_builds_unchanged():
-    m = Model(f"{REF}/models/transformer/yolov5s_fusion_transformerx3_vedai.yaml")
+    name = "yolov5s_fusion_transformerx3_vedai"
+    d = configs.named_config(name)
+    for part in ("backbone", "head"):
+        d[part] = [[f, n, m, ["None" if a is None else a for a in args]] for f, n, m, args in d[part]]
+    assert _config_sha256(d) == _reference_configs()["yaml_sha256"][name]["parsed"]
+    path = tmp_path / f"{name}.yaml"
+    path.write_text(yaml.safe_dump(d, sort_keys=False))
+    m = Model(str(path))
     assert m.yaml["nc"] == 9 and len(m.model) == 47
 
 
@@ -187,33 +205,24 @@ def test_product_never_imports_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, re.M), f
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_reference_pickled_checkpoint_loads_into_hip_modules(tmp_path):
-    """A checkpoint pickled by the REFERENCE code (whole nn.Module, train.py:850-860) un-pickles into
-    this package's classes once the module aliases are installed, with identical parameters."""
-    import subprocess
+def test_reference_pickled_checkpoint_loads_into_hip_modules():
+    """A checkpoint pickled by the REFERENCE code (whole nn.Module, ``.half()``, train.py:850-860; tests/golden/ref_ckpt_tiny.pt,
+    make_golden.py `ckpt`) un-pickles into this package's classes once the module aliases are installed, with identical parameters."""
     import sys
-    ck = tmp_path / "ref.pt"
-    script = f"""
-import sys, types, logging, torch
-for n in ("cv2", "torchvision", "seaborn"):
-    sys.modules.setdefault(n, types.ModuleType(n))
-sys.modules["cv2"].setNumThreads = lambda n: None
-sys.path.insert(0, {REF!r}); sys.path.insert(0, {ROOT!r}); logging.disable(logging.CRITICAL)
-import msod_amd
-from msod_amd.models.configs import named_config
-from models.yolo_test import Model
-m = Model(named_config("cfg2")).half()
-torch.save({{"model": m, "ema": None, "epoch": 3}}, {str(ck)!r})
-"""
-    subprocess.run([sys.executable, "-c", script], check=True, capture_output=True)
     from msod_amd import compat
-    model = compat.attempt_load(str(ck), map_location="cpu")
+    ck = os.path.join(ROOT, "tests", "golden", "ref_ckpt_tiny.pt")
+    model = compat.attempt_load(ck, map_location="cpu")
     assert type(model).__module__.startswith("msod_amd") and model.compute_dtype == torch.float32   # .float(), as the reference
     assert type(model.model[-1]).__name__ == "Detect" and not hasattr(model.model[1], "bn")     # fused
     assert all(p.dtype == torch.float32 for p in model.parameters())
     ups = [m for m in model.model if isinstance(m, torch.nn.Upsample)]
     assert len(ups) == 2 and all(type(u).__module__.startswith("msod_amd") for u in ups)
+    raw = torch.load(ck, map_location="cpu", weights_only=False)["model"].float()                    # the same pickle, not fused
+    unfused = Model(raw.yaml)
+    unfused.load_state_dict(raw.state_dict())
+    fused = unfused.fuse().state_dict()
+    assert set(fused) == set(model.state_dict())
+    assert all(torch.equal(fused[k], v) for k, v in model.state_dict().items())
     for name in ("models", "models.common", "models.yolo_test"):
         sys.modules.pop(name, None)
 
@@ -249,50 +258,12 @@ def test_concat_plan_routes_producers_into_concat_buffers():
     assert ups and not any(u in plan for u in ups)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_reference_graph_file_builds_over_this_packages_common():
-    """Strict form of the boundary ("models/yolo.py builds unchanged"): the reference's OWN
-    models/yolo_test.py (Model, parse_model with its eval() name lookup and `m is X` identity tests, forward_once,
-    Detect) imported unchanged, with only `models.common` resolved to this package, builds a reference yaml file;
-    its state-dict keys equal those of the reference-on-reference build; and a CPU forward reaches this package's
-    kernels' guard ("no CPU fallback") - i.e. the reference executor is driving the HIP-backed modules.  Run in a
-    subprocess: it puts the reference tree on sys.path."""
-    import subprocess
-    import sys
-    script = f"""
-import sys, types, logging, torch
-for n in ("cv2", "torchvision", "seaborn"):
-    sys.modules.setdefault(n, types.ModuleType(n))
-sys.modules["cv2"].setNumThreads = lambda n: None
-sys.path.insert(0, {REF!r}); sys.path.insert(0, {ROOT!r}); logging.disable(logging.CRITICAL)
-import msod_amd
-from msod_amd import compat
-compat.install_common_alias()
-from models.yolo_test import Model, Detect                      # the REFERENCE's graph file
-import models.yolo_test as ref_graph
-assert ref_graph.__file__.startswith({REF!r})
-m = Model({REF!r} + "/models/transformer/yolov5s_fusion_transformerx3_vedai.yaml")
-kinds = [type(l).__module__.split(".")[0] for l in m.model]
-assert type(m.model[0]).__name__ == "Focus" and type(m.model[0]).__module__.startswith("msod_amd"), kinds
-assert type(m.model[-1]) is Detect and Detect.__module__ == "models.yolo_test"
-assert sum(type(l).__name__ == "GPT" and type(l).__module__.startswith("msod_amd") for l in m.model) == 3
-assert any(type(l) is torch.nn.Upsample for l in m.model)          # the reference's plain torch Upsample stays
-from msod_amd.models.yolo_test import Model as Ours
-from msod_amd.models.configs import named_config
-ours = Ours(named_config("yolov5s_fusion_transformerx3_vedai"))
-assert list(m.state_dict().keys()) == list(ours.state_dict().keys())
-assert all(a.shape == b.shape for a, b in zip(m.state_dict().values(), ours.state_dict().values()))
-try:
-    m.eval()(torch.zeros(1, 3, 64, 64), torch.zeros(1, 3, 64, 64))
-    raise SystemExit("CPU forward did not raise")
-except RuntimeError as e:
-    assert "no CPU fallback" in str(e), e
-m.fuse()                                                         # the reference's fuse(): type(m) is Conv, .bn, .fuseforward
-assert not hasattr(m.model[1], "bn") and m.model[1].conv.bias is not None
-print("STRICT-FORM-OK")
-"""
-    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True)
-    assert r.returncode == 0 and "STRICT-FORM-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+def test_state_dict_layout_equals_the_reference_build():
+    """The reference's own Model built from yolov5s_fusion_transformerx3_vedai.yaml has exactly this package's state-dict keys,
+    in the same order, with the same shapes (layout recorded by make_golden.py `configs`), so reference checkpoints load as they are."""
+    want = [(k, tuple(s)) for k, s in _reference_configs()["state_dict_layout_yolov5s_fusion_transformerx3_vedai"]]
+    ours = Model(configs.named_config("yolov5s_fusion_transformerx3_vedai"))
+    assert [(k, tuple(v.shape)) for k, v in ours.state_dict().items()] == want
 
 
 def test_bench_parity_check_flags_a_wrong_batch():
@@ -316,6 +287,33 @@ def test_bench_parity_check_flags_a_wrong_batch():
     assert not worse["ok"]
     assert bench.parity_at_bench_shape("f16", noise(0.002), want)["ok"] and not bench.parity_at_bench_shape("f16", noise(0.1), want)["ok"]
     assert bench.parity_at_bench_shape("f32", noise(1e-5), want)["ok"] and not bench.parity_at_bench_shape("f32", noise(0.01), want)["ok"]
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files of pred and the raw maps; a batch above the 64 MB budget keeps the same
+    seeded subset of pairs in every array, identical from call to call; a batch within the budget is written whole."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    b = 40
+    pred = torch.randn(b, 25200, 8, generator=g).bfloat16()
+    raw = [torch.randn(b, 3, s, s, 8, generator=g).bfloat16() for s in (80, 40, 20)]
+    a = bench.dump_outputs(str(tmp_path / "a"), pred, raw)
+    again = bench.dump_outputs(str(tmp_path / "b"), pred, raw)
+    assert a["rows"] == again["rows"] and a["rows"] == sorted(a["rows"]) and 0 < len(a["rows"]) < b
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["pred.npy", "raw0.npy", "raw1.npy", "raw2.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    rows = torch.tensor(a["rows"])
+    for name, t in (("pred", pred), *((f"raw{i}", r) for i, r in enumerate(raw))):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, t[rows].float().numpy())
+        assert np.array_equal(got, np.load(tmp_path / "b" / f"{name}.npy"))
+    small = bench.dump_outputs(str(tmp_path / "c"), pred[:2], [r[:2] for r in raw])
+    assert small["rows"] == [0, 1] and np.array_equal(np.load(tmp_path / "c" / "pred.npy"), pred[:2].float().numpy())
 
 
 def test_shader_clock_summary_arithmetic():
