@@ -5,21 +5,39 @@
 // BatchNorm2d in training mode (torch semantics): per channel c over the M = B*H*W rows of the conv output
 //   mean = sum(x)/M,  var = sum((x-mean)^2)/M (biased),  y = (x-mean)/sqrt(var+eps)*gamma + beta
 //   running_mean = (1-m)*running_mean + m*mean,  running_var = (1-m)*running_var + m*var*M/(M-1)
-// Three launches, deterministic (no atomics): per-slab partial sums (fp32 inside a slab of <= 4096 rows, Welford-free
-// because the slab means are combined in double), a finalize kernel (double), and the apply kernel.
+// Three launches, deterministic (no atomics): per-slab partial sums (fp32 inside a slab of <= 4096 rows, centred on the slab's
+// own mean; the slabs are combined in double), a finalize kernel (double), and the apply kernel.
 #include "cft_common.h"
 
 __global__ void __launch_bounds__(1024) bn_partial_kernel(const float* __restrict__ x, long ldx, long xoff, long M, int G, int rpp,
                                                           long rows_per_blk, float* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float4* red = reinterpret_cast<float4*>(smem);           // [rpp][G] sums, then [rpp][G] sums of squares
+  float4* red = reinterpret_cast<float4*>(smem);           // [rpp][G] sums, then [rpp][G] sums of squares; [G] slab pivots behind them
+  float4* piv = red + 2 * rpp * G;
   const int g = threadIdx.x % G, r = threadIdx.x / G;
   const long m0 = (long)blockIdx.x * rows_per_blk;
   const long m1 = (m0 + rows_per_blk < M) ? m0 + rows_per_blk : M;
+  // Two passes over the slab (it is re-read from cache): the fp32 mean of the slab, then sums of (x - that mean) and of its
+  // squares.  A pivot taken from the data (e.g. one row) brings the cancellation of E[x^2] - mean^2 back whenever that row lies
+  // far from its channel's mean; the slab mean is within a few ulps of |mean| of the true one.  Fixed order: deterministic.
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 0.f);
-  // sums of (x - pivot): the pivot (row 0 of the tensor, the same for every slab) removes the cancellation of
-  // E[x^2] - mean^2 for channels with |mean| >> std
-  const float4 pv = *reinterpret_cast<const float4*>(x + xoff + g * 4L);
+  for (long m = m0 + r; m < m1; m += rpp) {
+    const float4 v = *reinterpret_cast<const float4*>(x + m * ldx + xoff + g * 4L);
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  red[r * G + g] = s;
+  __syncthreads();
+  if (r == 0) {
+    for (int k = 1; k < rpp; ++k) {
+      const float4 a = red[k * G + g];
+      s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
+    }
+    const float inv_n = 1.0f / (float)(m1 - m0);
+    piv[g] = make_float4(s.x * inv_n, s.y * inv_n, s.z * inv_n, s.w * inv_n);
+  }
+  __syncthreads();
+  const float4 pv = piv[g];
+  s = make_float4(0.f, 0.f, 0.f, 0.f);
   for (long m = m0 + r; m < m1; m += rpp) {
     float4 v = *reinterpret_cast<const float4*>(x + m * ldx + xoff + g * 4L);
     v.x -= pv.x; v.y -= pv.y; v.z -= pv.z; v.w -= pv.w;
@@ -35,28 +53,36 @@ __global__ void __launch_bounds__(1024) bn_partial_kernel(const float* __restric
       s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
       q.x += b.x; q.y += b.y; q.z += b.z; q.w += b.w;
     }
-    float4* o = reinterpret_cast<float4*>(part + (long)blockIdx.x * 2 * G * 4);
-    o[g] = s;
-    o[G + g] = q;
+    float4* o = reinterpret_cast<float4*>(part + (long)blockIdx.x * 3 * G * 4);
+    o[g] = pv;
+    o[G + g] = s;
+    o[2 * G + g] = q;
   }
 }
 
-__global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restrict__ x, long xoff, const float* __restrict__ part, int nblk, int C, int Cp, long M,
+__global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restrict__ part, int nblk, long rows_per_blk, int C, int Cp, long M,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float* __restrict__ running_mean, float* __restrict__ running_var,
                                                           float momentum, float eps, float* __restrict__ scale_shift) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= Cp) return;
   if (c >= C) { scale_shift[c] = 0.f; scale_shift[Cp + c] = 0.f; return; }   // padding channels of the GEMM output
-  double s = 0.0, q = 0.0;
+  // slab k: n_k rows, pivot p_k, s_k = sum(x - p_k), q_k = sum((x - p_k)^2) -> mean p_k + s_k / n_k, M2_k = q_k - s_k^2 / n_k;
+  // combined in slab order in double (Chan et al.'s pairwise update)
+  double n = 0.0, mean = 0.0, m2 = 0.0;
   for (int k = 0; k < nblk; ++k) {
-    s += (double)part[(long)k * 2 * Cp + c];
-    q += (double)part[(long)k * 2 * Cp + Cp + c];
+    const long r0 = (long)k * rows_per_blk;
+    const double nk = (double)((M - r0) < rows_per_blk ? (M - r0) : rows_per_blk);
+    const double sk = (double)part[(long)k * 3 * Cp + Cp + c], qk = (double)part[(long)k * 3 * Cp + 2 * Cp + c];
+    const double mk = (double)part[(long)k * 3 * Cp + c] + sk / nk;
+    double m2k = qk - sk * sk / nk;
+    m2k = m2k < 0.0 ? 0.0 : m2k;
+    const double nn = n + nk, d = mk - mean;
+    mean += d * (nk / nn);
+    m2 += m2k + d * d * (n * nk / nn);
+    n = nn;
   }
-  const double dm = s / (double)M;                  // mean of (x - pivot)
-  double var = q / (double)M - dm * dm;
-  var = var < 0.0 ? 0.0 : var;
-  const double mean = (double)x[xoff + c] + dm;
+  const double var = m2 / (double)M;
   const float sc = gamma[c] * (float)(1.0 / sqrt(var + (double)eps));
   scale_shift[c] = sc;
   scale_shift[Cp + c] = beta[c] - (float)mean * sc;
@@ -97,7 +123,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__
 extern "C" long cft_batchnorm_train_workspace(long M, int C) {
   const int Cp = (C + 7) / 8 * 8;
   const long nblk = (M + 4095) / 4096;
-  return (nblk * 2 * Cp + 2 * Cp) * (long)sizeof(float);
+  return (nblk * 3 * Cp + 2 * Cp) * (long)sizeof(float);
 }
 
 extern "C" int cft_batchnorm_train(const float* x, int ldx, int xoff, long M, int C,
@@ -121,13 +147,13 @@ extern "C" int cft_batchnorm_train(const float* x, int ldx, int xoff, long M, in
   hipStream_t s = as_stream(stream);
   float* part = reinterpret_cast<float*>(workspace);
   const long nblk = (M + 4095) / 4096;
-  float* scale_shift = part + nblk * 2 * Cp;
+  float* scale_shift = part + nblk * 3 * Cp;
   const int G = Cp / 4;
   int rpp = 1024 / G;
   rpp = rpp < 1 ? 1 : (rpp > 16 ? 16 : rpp);
   CFT_REQUIRE(G <= 1024, "cft_batchnorm_train: too many channels for one workgroup");
-  hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)nblk), dim3(G * rpp), (size_t)2 * rpp * G * 16, s, x, (long)ldx, (long)xoff, M, G, rpp, 4096L, part);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((Cp + 255) / 256), dim3(256), 0, s, x, (long)xoff, part, (int)nblk, C, Cp, M, gamma, beta, running_mean, running_var,
+  hipLaunchKernelGGL(bn_partial_kernel, dim3((unsigned)nblk), dim3(G * rpp), (size_t)(2 * rpp + 1) * G * 16, s, x, (long)ldx, (long)xoff, M, G, rpp, 4096L, part);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((Cp + 255) / 256), dim3(256), 0, s, part, (int)nblk, 4096L, C, Cp, M, gamma, beta, running_mean, running_var,
                      momentum, eps, scale_shift);
   const int gpp = Cp / ge;
   long g = (M * gpp + 255) / 256;

@@ -719,7 +719,8 @@ def batchnorm_train(y32, C, bn, act, residual=None, out=None, out_dtype=None):
     if tuple(out.shape) != (B, C, H, W):
         raise ValueError(f"batchnorm_train: out has shape {tuple(out.shape)}, expected {(B, C, H, W)}")
     ldy = _view_ld(out, "batchnorm_train out")
-    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+    track = bn.track_running_stats and bn.running_mean is not None
+    for t in (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var) if track else ()):     # (no running statistics: track_running_stats=False)
         if t.dtype != torch.float32 or not t.is_contiguous() or t.device != y32.device:
             raise TypeError("batchnorm_train: BatchNorm parameters / running statistics must be contiguous fp32 tensors on the GPU")
     rp, ldr, rdt = None, 0, CFT_F32
@@ -730,7 +731,6 @@ def batchnorm_train(y32, C, bn, act, residual=None, out=None, out_dtype=None):
     lib = _lib.load()
     M = B * H * W
     ws = torch.empty((lib.cft_batchnorm_train_workspace(M, C),), dtype=torch.uint8, device=y32.device)
-    track = bn.track_running_stats and bn.running_mean is not None
     if bn.momentum is not None:
         mom = float(bn.momentum)
     else:   # torch: momentum=None is the cumulative moving average, factor 1 / num_batches_tracked (after the increment)
