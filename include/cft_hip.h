@@ -247,6 +247,41 @@ int cft_gpt_upsample_add2(const float* tokens, const void* base0, int ldb0, int 
                           int B, int H, int W, int C, int dtype, void* stream);
 
 /*
+ * The CFT block on a vert_anchors x horz_anchors grid (models/common.py:549-639 with GPT(..., vert_anchors=va, horz_anchors=ha)):
+ * T = 2 * va * ha tokens, RGB cells 0 .. va*ha-1 then IR, row-major within a stream.  Supported: 1 <= va, ha, va * ha <= 1024.
+ * At (8, 8) each entry point below is bit-identical to its 8x8 counterpart above.
+ *
+ * Tokeniser (replaces the AdaptiveAvgPool2d((va, ha)) + flatten + cat + pos_emb of models/common.py:606-621):
+ *   tokens[b, s*va*ha + i*ha + j, c] = mean(window(i,j) of stream s)[c] + pos_emb[s*va*ha + i*ha + j, c]
+ * window rows [floor(i*H/va), ceil((i+1)*H/va)), columns [floor(j*W/ha), ceil((j+1)*W/ha)) (overlapping when H < va or W < ha).
+ * rgb/ir: dtype NHWC; pos_emb float [2*va*ha, C]; tokens: float [B, 2*va*ha, C].
+ */
+int cft_gpt_tokenize_grid(const void* rgb, int ld_rgb, int off_rgb, const void* ir, int ld_ir, int off_ir,
+                          const float* pos_emb, float* tokens, int B, int H, int W, int C, int va, int ha,
+                          int dtype, void* stream);
+
+/*
+ * Multi-head self-attention core over any token count 1 <= T <= 2048 (models/common.py:491-510), flash-style (64-key tiles, online
+ * softmax; numerics in csrc/attention_tokens.hip).  qkv : dtype [B*T, 3*heads*dkp], out : dtype [B*T, heads*dkp], the layout of
+ * cft_attention.  Training dropout index ((b*heads + h)*T + q)*T + k (cft_attention's at T = 128).
+ */
+int cft_attention_tokens(const void* qkv, void* out, int B, int T, int heads, int dk, int dkp,
+                         int dtype, float attn_pdrop, unsigned long long seed, void* stream);
+
+/*
+ * De-tokeniser on a va x ha grid (models/common.py:626-637 + Add2 :238-243): cft_gpt_upsample_add with
+ * bilinear_{va x ha -> H x W, align_corners=False}; tokens float [B, 2*va*ha, C], contiguous, 16-byte aligned.
+ */
+int cft_gpt_upsample_add_grid(const float* tokens, int s, const void* base, int ldb, int boff,
+                              void* out, int ldo, int ooff, int B, int H, int W, int C, int va, int ha,
+                              int dtype, void* stream);
+
+/* Both streams + Add2 twice (+ Add, models/common.py:228-229) on a va x ha grid: cft_gpt_upsample_add2 with the grid above. */
+int cft_gpt_upsample_add2_grid(const float* tokens, const void* base0, int ldb0, int boff0, const void* base1, int ldb1, int boff1,
+                               void* out0, int ldo0, int ooff0, void* out1, int ldo1, int ooff1, void* sum, int lds, int soff,
+                               int B, int H, int W, int C, int va, int ha, int dtype, void* stream);
+
+/*
  * Detect decode (models/yolo_test.py:47-57).  logits: float [B,ny,nx,ldl] holding na*no valid
  * channels (channel = a*no + o), the output of the 1x1 conv.  Writes
  *   raw [B,na,ny,nx,no]            = logits permuted (the reference's x[i])

@@ -704,6 +704,185 @@ extern "C" int cft_gpt_upsample_add2(const float* tokens, const void* base0, int
   return cft_check_launch("gpt_upsample_add2_kernel");
 }
 
+// ------------------------------------------------------------------------------- CFT tokeniser / de-tokeniser on a va x ha grid
+// The same as gpt_tokenize_kernel / gpt_upsample_add{,2}_kernel for a vert_anchors x horz_anchors grid (T = 2 * va * ha tokens, RGB
+// cells 0 .. va*ha-1 then IR).  At (8, 8) every output element is formed by the same expression as the 8x8 kernels: bit-identical.
+template <typename T>
+__global__ void __launch_bounds__(256) gpt_tokenize_grid_kernel(const unsigned char* rgb, long ld_rgb_b, long off_rgb_b,
+                                                                const unsigned char* ir, long ld_ir_b, long off_ir_b,
+                                                                const float* __restrict__ pos_emb, float* __restrict__ tokens,
+                                                                int H, int W, int C, int va, int ha) {
+  constexpr int GE = Elem<T>::GE;
+  const int ncell = va * ha, ntok = 2 * ncell;
+  const int b = blockIdx.x / ntok, cell = blockIdx.x - b * ntok;
+  const int s = cell >= ncell ? 1 : 0, r = cell - s * ncell;
+  const int i = r / ha, j = r - i * ha;
+  const int h0 = (i * H) / va, h1 = ((i + 1) * H + va - 1) / va;     // AdaptiveAvgPool2d windows (overlap when H < va)
+  const int w0 = (j * W) / ha, w1 = ((j + 1) * W + ha - 1) / ha;
+  const unsigned char* src = s ? ir : rgb;
+  const long ldb = s ? ld_ir_b : ld_rgb_b, offb = s ? off_ir_b : off_rgb_b;
+  const float inv = 1.0f / (float)((h1 - h0) * (w1 - w0));
+  for (int cg = threadIdx.x; cg < C / GE; cg += blockDim.x) {
+    float acc[GE];
+#pragma unroll
+    for (int e = 0; e < GE; ++e) acc[e] = 0.f;
+    for (int y = h0; y < h1; ++y)
+      for (int x = w0; x < w1; ++x) {
+        float f[GE];
+        Elem<T>::unpack(*reinterpret_cast<const gran_t*>(src + (((long)b * H + y) * W + x) * ldb + offb + cg * 16L), f);
+#pragma unroll
+        for (int e = 0; e < GE; ++e) acc[e] += f[e];
+      }
+    float* o = tokens + ((long)b * ntok + cell) * C + cg * GE;
+    const float* pe = pos_emb + (long)cell * C + cg * GE;
+#pragma unroll
+    for (int e = 0; e < GE; ++e) o[e] = acc[e] * inv + pe[e];
+  }
+}
+
+extern "C" int cft_gpt_tokenize_grid(const void* rgb, int ld_rgb, int off_rgb, const void* ir, int ld_ir, int off_ir,
+                                     const float* pos_emb, float* tokens, int B, int H, int W, int C, int va, int ha,
+                                     int dtype, void* stream) {
+  CFT_REQUIRE(rgb && ir && pos_emb && tokens, "cft_gpt_tokenize_grid: null pointer");
+  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_tokenize_grid: bad dtype");
+  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
+  CFT_REQUIRE(C % ge == 0 && ld_rgb % ge == 0 && off_rgb % ge == 0 && ld_ir % ge == 0 && off_ir % ge == 0, "cft_gpt_tokenize_grid: not granule aligned");
+  CFT_REQUIRE(B > 0 && H >= 1 && W >= 1, "cft_gpt_tokenize_grid: bad shape");
+  CFT_REQUIRE(va >= 1 && ha >= 1 && va * ha <= 1024, "cft_gpt_tokenize_grid: anchor grid must satisfy 1 <= va, ha and va * ha <= 1024");
+  CFT_REQUIRE((long)B * 2 * va * ha < (1L << 31), "cft_gpt_tokenize_grid: too many tokens");
+  int threads = C / ge;
+  threads = threads < 64 ? 64 : (threads > 256 ? 256 : ((threads + 63) / 64) * 64);
+  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gpt_tokenize_grid_kernel<T>, dim3(B * 2 * va * ha), dim3(threads), 0, as_stream(stream),
+                                                   (const unsigned char*)rgb, (long)ld_rgb * es, (long)off_rgb * es,
+                                                   (const unsigned char*)ir, (long)ld_ir * es, (long)off_ir * es, pos_emb, tokens, H, W, C, va, ha));
+  return cft_check_launch("gpt_tokenize_grid_kernel");
+}
+
+// De-tokeniser on a va x ha grid: one workgroup per output image row (b, y), like gpt_upsample_add_kernel.  The y-blended token row
+// ([ha][CW] floats per stream) is staged in LDS one channel chunk of CW channels at a time, so any ha * C fits (CW = C when the whole
+// row fits the budget).  DUAL = false: stream s of tokens, optional base (one-stream form).  DUAL = true: both streams, both bases,
+// optional sum = out0 + out1 from the unrounded fp32 values (the two-stream + Add2 (+ Add) form of gpt_upsample_add2_kernel).
+template <typename T, bool DUAL>
+__global__ void __launch_bounds__(256) gpt_upsample_grid_kernel(const float* __restrict__ tokens, int s,
+                                                                const unsigned char* base0, long ldb0_b, long boff0_b,
+                                                                const unsigned char* base1, long ldb1_b, long boff1_b,
+                                                                unsigned char* out0, long ldo0_b, long ooff0_b,
+                                                                unsigned char* out1, long ldo1_b, long ooff1_b,
+                                                                unsigned char* sum, long lds_b, long soff_b,
+                                                                int B, int H, int W, int C, int va, int ha, int CW) {
+  constexpr int GE = Elem<T>::GE;
+  constexpr int NS = DUAL ? 2 : 1;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* R = reinterpret_cast<float*>(smem);          // [NS][ha][CW]
+  const int ncell = va * ha;
+  const int b = blockIdx.x / H, y = blockIdx.x - b * H;
+  float fy = ((float)y + 0.5f) * ((float)va / (float)H) - 0.5f; fy = fy < 0.f ? 0.f : fy;
+  const int y0 = (int)fy, y1 = y0 + (y0 < va - 1 ? 1 : 0);
+  const float ly = fy - (float)y0, hy = 1.f - ly;
+  const float sx = (float)ha / (float)W;
+  const long rowpix = ((long)b * H + y) * W;
+  for (int c0 = 0; c0 < C; c0 += CW) {
+    const int cw = C - c0 < CW ? C - c0 : CW;
+    const int q4 = cw / 4;                            // float4 per cell row of the chunk
+    if (c0 > 0) __syncthreads();                      // the previous chunk is consumed
+#pragma unroll
+    for (int ss = 0; ss < NS; ++ss) {
+      const int st = DUAL ? ss : s;
+      const float* t0 = tokens + ((long)b * 2 * ncell + st * ncell + y0 * ha) * C + c0;
+      const float* t1 = tokens + ((long)b * 2 * ncell + st * ncell + y1 * ha) * C + c0;
+      for (int i = threadIdx.x; i < ha * q4; i += blockDim.x) {
+        const int x = i / q4, k = i - x * q4;
+        const float4 a = reinterpret_cast<const float4*>(t0 + (long)x * C)[k], c = reinterpret_cast<const float4*>(t1 + (long)x * C)[k];
+        reinterpret_cast<float4*>(R + (ss * ha + x) * CW)[k] = make_float4(hy * a.x + ly * c.x, hy * a.y + ly * c.y, hy * a.z + ly * c.z, hy * a.w + ly * c.w);
+      }
+    }
+    __syncthreads();
+    const int gpc = cw / GE;
+    for (int idx = threadIdx.x; idx < W * gpc; idx += blockDim.x) {
+      const int x = idx / gpc, cgl = idx - x * gpc;
+      const long cb = (long)(c0 + cgl * GE) * sizeof(T);
+      float fx = ((float)x + 0.5f) * sx - 0.5f; fx = fx < 0.f ? 0.f : fx;
+      const int x0 = (int)fx, x1 = x0 + (x0 < ha - 1 ? 1 : 0);
+      const float lx = fx - (float)x0, hx = 1.f - lx;
+      const long pix = rowpix + x;
+      const float* r0 = R + x0 * CW + cgl * GE;
+      const float* r1 = R + x1 * CW + cgl * GE;
+      float v0[GE];
+      if (base0 != nullptr) {
+        Elem<T>::unpack(*reinterpret_cast<const gran_t*>(base0 + pix * ldb0_b + boff0_b + cb), v0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < GE; ++e) v0[e] = 0.f;
+      }
+      if constexpr (DUAL) {
+        float v1[GE];
+        Elem<T>::unpack(*reinterpret_cast<const gran_t*>(base1 + pix * ldb1_b + boff1_b + cb), v1);
+#pragma unroll
+        for (int e = 0; e < GE; ++e) {
+          v0[e] += hx * r0[e] + lx * r1[e];
+          v1[e] += hx * r0[ha * CW + e] + lx * r1[ha * CW + e];
+        }
+        *reinterpret_cast<gran_t*>(out0 + pix * ldo0_b + ooff0_b + cb) = Elem<T>::pack(v0);
+        *reinterpret_cast<gran_t*>(out1 + pix * ldo1_b + ooff1_b + cb) = Elem<T>::pack(v1);
+        if (sum != nullptr) {
+#pragma unroll
+          for (int e = 0; e < GE; ++e) v0[e] += v1[e];
+          *reinterpret_cast<gran_t*>(sum + pix * lds_b + soff_b + cb) = Elem<T>::pack(v0);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < GE; ++e) v0[e] += hx * r0[e] + lx * r1[e];
+        *reinterpret_cast<gran_t*>(out0 + pix * ldo0_b + ooff0_b + cb) = Elem<T>::pack(v0);
+      }
+    }
+  }
+}
+
+// LDS budget of the de-tokeniser's staged row: 64 KiB; channel chunk = the widest multiple of 8 channels that fits.
+static inline int gpt_upsample_grid_chunk(int C, int ha, int ns) {
+  int cw = (16 * 1024) / (ns * ha);
+  cw -= cw % 8;
+  return C < cw ? C : cw;
+}
+
+extern "C" int cft_gpt_upsample_add_grid(const float* tokens, int s, const void* base, int ldb, int boff,
+                                         void* out, int ldo, int ooff, int B, int H, int W, int C, int va, int ha,
+                                         int dtype, void* stream) {
+  CFT_REQUIRE(tokens && out, "cft_gpt_upsample_add_grid: null pointer");
+  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add_grid: bad dtype");
+  CFT_REQUIRE(s == 0 || s == 1, "cft_gpt_upsample_add_grid: stream index must be 0 or 1");
+  CFT_REQUIRE(va >= 1 && ha >= 1 && va * ha <= 1024, "cft_gpt_upsample_add_grid: anchor grid must satisfy 1 <= va, ha and va * ha <= 1024");
+  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
+  CFT_REQUIRE(C % ge == 0 && ldo % ge == 0 && ooff % ge == 0 && (base == nullptr || (ldb % ge == 0 && boff % ge == 0)), "cft_gpt_upsample_add_grid: not granule aligned");
+  CFT_REQUIRE(C % 4 == 0 && C <= 2048 && B > 0 && H >= 1 && W >= 1 && (long)B * H < (1L << 31), "cft_gpt_upsample_add_grid: C must be a multiple of 4, <= 2048");
+  const int cw = gpt_upsample_grid_chunk(C, ha, 1);
+  const size_t smem = (size_t)ha * cw * sizeof(float);
+  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gpt_upsample_grid_kernel<T, false>), dim3(B * H), dim3(256), smem, as_stream(stream), tokens, s,
+                                                   (const unsigned char*)base, (long)ldb * es, (long)boff * es, nullptr, 0L, 0L,
+                                                   (unsigned char*)out, (long)ldo * es, (long)ooff * es, nullptr, 0L, 0L, nullptr, 0L, 0L,
+                                                   B, H, W, C, va, ha, cw));
+  return cft_check_launch("gpt_upsample_grid_kernel");
+}
+
+extern "C" int cft_gpt_upsample_add2_grid(const float* tokens, const void* base0, int ldb0, int boff0, const void* base1, int ldb1, int boff1,
+                                          void* out0, int ldo0, int ooff0, void* out1, int ldo1, int ooff1, void* sum, int lds, int soff,
+                                          int B, int H, int W, int C, int va, int ha, int dtype, void* stream) {
+  CFT_REQUIRE(tokens && base0 && base1 && out0 && out1, "cft_gpt_upsample_add2_grid: null pointer");
+  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add2_grid: bad dtype");
+  CFT_REQUIRE(va >= 1 && ha >= 1 && va * ha <= 1024, "cft_gpt_upsample_add2_grid: anchor grid must satisfy 1 <= va, ha and va * ha <= 1024");
+  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
+  CFT_REQUIRE(C % ge == 0 && ldb0 % ge == 0 && boff0 % ge == 0 && ldb1 % ge == 0 && boff1 % ge == 0 && ldo0 % ge == 0 && ooff0 % ge == 0 &&
+              ldo1 % ge == 0 && ooff1 % ge == 0 && (sum == nullptr || (lds % ge == 0 && soff % ge == 0)), "cft_gpt_upsample_add2_grid: not granule aligned");
+  CFT_REQUIRE(C % 4 == 0 && C <= 2048 && B > 0 && H >= 1 && W >= 1 && (long)B * H < (1L << 31), "cft_gpt_upsample_add2_grid: C must be a multiple of 4, <= 2048");
+  const int cw = gpt_upsample_grid_chunk(C, ha, 2);
+  const size_t smem = (size_t)2 * ha * cw * sizeof(float);
+  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gpt_upsample_grid_kernel<T, true>), dim3(B * H), dim3(256), smem, as_stream(stream), tokens, 0,
+                                                   (const unsigned char*)base0, (long)ldb0 * es, (long)boff0 * es, (const unsigned char*)base1, (long)ldb1 * es, (long)boff1 * es,
+                                                   (unsigned char*)out0, (long)ldo0 * es, (long)ooff0 * es, (unsigned char*)out1, (long)ldo1 * es, (long)ooff1 * es,
+                                                   (unsigned char*)sum, (long)lds * es, (long)soff * es, B, H, W, C, va, ha, cw));
+  return cft_check_launch("gpt_upsample_grid_kernel");
+}
+
 // ------------------------------------------------------------------------------- Detect decode
 __global__ void __launch_bounds__(256) detect_decode_kernel(const float* __restrict__ logits, int ldl, float* __restrict__ raw,
                                                             float* __restrict__ pred, const float* __restrict__ anchors,

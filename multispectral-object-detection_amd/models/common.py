@@ -52,13 +52,13 @@ class _Pending:
 
 
 class PendingBilinear(_Pending):
-    """GPT output stream ``s``: bilinear(tokens 8x8 -> HxW).  ``Add2`` fuses it with its add."""
+    """GPT output stream ``s``: bilinear(tokens va x ha -> HxW), ``grid`` = (va, ha).  ``Add2`` fuses it with its add."""
 
-    def __init__(self, tokens, s, H, W, dtype):
-        self.tokens, self.s, self.H, self.W, self.dtype = tokens, s, H, W, dtype
+    def __init__(self, tokens, s, H, W, dtype, grid=ops.ANCHOR_GRID):
+        self.tokens, self.s, self.H, self.W, self.dtype, self.grid = tokens, s, H, W, dtype, tuple(grid)
 
     def materialize(self, base=None):
-        return ops.gpt_upsample_add(self.tokens, self.s, base, self.H, self.W, self.dtype)
+        return ops.gpt_upsample_add(self.tokens, self.s, base, self.H, self.W, self.dtype, grid=self.grid)
 
     @property
     def shape(self):
@@ -501,16 +501,16 @@ class SelfAttention(_Packed):
         out.flops_per_row = 2.0 * d * h * dk
         return qkv, out, dkp
 
-    def forward(self, x, attention_mask=None, attention_weights=None, residual=None, splitk=False):
-        """x: [B*128, d] in the compute dtype.  Returns out_proj(attn) (+ residual, fp32, in place).  ``splitk`` (the transformer block's
+    def forward(self, x, attention_mask=None, attention_weights=None, residual=None, splitk=False, ntok=128):
+        """x: [B*ntok, d] in the compute dtype (``ntok`` tokens per image: 2 * vert_anchors * horz_anchors of the GPT).  Returns out_proj(attn) (+ residual, fp32, in place).  ``splitk`` (the transformer block's
         inference path): returns the out_proj's fp32 split-K partial sums [s, rows, d] when ``ops.splitk_choice`` splits it (``residual`` is
         then NOT updated - ``ops.layernorm_reduce`` does that), else None after the in-place update."""
         if attention_mask is not None or attention_weights is not None:
             raise NotImplementedError("attention_mask / attention_weights are unused by GPT (reference :497-500)")
         qkv_w, out_w, dkp = self._packed(x.dtype, x.device)
-        B = x.shape[0] // 128
+        B = x.shape[0] // ntok
         qkv = ops.linear(x, qkv_w)
-        att = ops.attention(qkv, B, self.h, self.d_k, dkp, pdrop=self.attn_drop.p if self.training else 0.0)
+        att = ops.attention(qkv, B, self.h, self.d_k, dkp, pdrop=self.attn_drop.p if self.training else 0.0, T=ntok)
         if self.training and self.resid_drop.p > 0 and residual is not None:
             proj = ops.linear(att, out_w, out_dtype=torch.float32)          # resid_drop(out_proj(.)) then the residual add
             ops.dropout_(proj, self.resid_drop.p)
@@ -526,7 +526,7 @@ class SelfAttention(_Packed):
 
 class myTransformerBlock(_Packed):
     """Pre-LN transformer block (reference models/common.py:516-546).  ``x`` is the fp32 residual
-    stream [B*128, d]; it is updated in place by the two GEMM epilogues."""
+    stream [B*ntok, d]; it is updated in place by the two GEMM epilogues."""
 
     def __init__(self, d_model, d_k, d_v, h, block_exp, attn_pdrop, resid_pdrop):
         super().__init__()
@@ -548,7 +548,7 @@ class myTransformerBlock(_Packed):
 
     splitk = True        # inference: out_proj / fc2 as split-K GEMMs where ops.splitk_choice splits them (GPT.splitk switches all blocks; A/B)
 
-    def forward(self, x, compute_dtype=torch.bfloat16, pending=None):
+    def forward(self, x, compute_dtype=torch.bfloat16, pending=None, ntok=128):
         """``pending``: fp32 split-K partial sums of the PREVIOUS block's fc2 that are not yet folded into ``x`` (or None).  Returns this
         block's own pending partial sums (or None when its fc2 updated ``x`` in place); ``GPT.forward`` hands them to the next block /
         ``ln_f``.  Each LayerNorm that follows a split GEMM is ``ops.layernorm_reduce``: x += partial sums (fixed order), then LayerNorm."""
@@ -562,9 +562,9 @@ class myTransformerBlock(_Packed):
         y = norm(pending, ln[0], ln[1], self.ln_input.eps)
         parts = None
         if split:
-            parts = self.sa(y, residual=x, splitk=True)           # x += out_proj(attention(LN(x))), or its partial sums
+            parts = self.sa(y, residual=x, splitk=True, ntok=ntok)   # x += out_proj(attention(LN(x))), or its partial sums
         else:
-            self.sa(y, residual=x)
+            self.sa(y, residual=x, ntok=ntok)
         y = norm(parts, ln[2], ln[3], self.ln_output.eps)
         hid = ops.linear(y, fc1, act=ACT_GELU)
         pd = self.mlp[3].p if (self.training and len(self.mlp) > 3) else 0.0
@@ -613,9 +613,25 @@ class GPT(_Packed):
     def _pack(self, dtype, device):   # fp32 copies of what the kernels read through raw pointers (fp16 after model.half())
         return _f32(self.pos_emb, device), _f32(self.ln_f.weight, device), _f32(self.ln_f.bias, device)
 
+    def check_supported(self, C=None):
+        """Raise NotImplementedError, naming the limit, for a configuration outside what the kernels take: 1 <= vert_anchors,
+        horz_anchors, vert_anchors * horz_anchors <= 1024 (T <= 2048 tokens), head width d_model / h <= 256, and (grids other than the
+        8 x 8 default) d_model <= 2048."""
+        grid = (int(self.vert_anchors), int(self.horz_anchors))
+        if grid != (self.vert_anchors, self.horz_anchors):
+            raise NotImplementedError(f"anchor grid {self.vert_anchors}x{self.horz_anchors}: vert_anchors / horz_anchors must be integers")
+        ops._grid(grid)
+        blk = self.trans_blocks[0] if len(self.trans_blocks) else None
+        if blk is not None and blk.sa.d_k > 256:
+            raise NotImplementedError(f"GPT head width d_model / h = {blk.sa.d_k}: the attention kernels take head widths <= 256")
+        C = self.n_embd if C is None else C
+        if grid != ops.ANCHOR_GRID and C > 2048:
+            raise NotImplementedError(f"GPT d_model = {C} on a {grid[0]}x{grid[1]} anchor grid: the kernels take d_model <= 2048")
+        return grid
+
     def forward(self, x):
-        if self.vert_anchors != 8 or self.horz_anchors != 8:
-            raise NotImplementedError("the CFT kernels are specialised for the 8x8 anchor grid (128 tokens)")
+        grid = self.check_supported()
+        T = 2 * grid[0] * grid[1]
         rgb, ir = resolve(x[0]), resolve(x[1])
         assert rgb.shape[0] == ir.shape[0]
         if rgb.shape != ir.shape or rgb.dtype != ir.dtype:
@@ -623,18 +639,19 @@ class GPT(_Packed):
         B, C, H, W = rgb.shape
         dtype = rgb.dtype
         pos_emb, lnf_w, lnf_b = self._packed(dtype, rgb.device)
-        tok = ops.gpt_tokenize(rgb, ir, pos_emb)                 # fp32 [B,128,C], pos_emb added
+        tok = ops.gpt_tokenize(rgb, ir, pos_emb, grid=grid)      # fp32 [B,T,C], pos_emb added
         if self.training:
             ops.dropout_(tok, self.drop.p)                       # self.drop(pos_emb + token_embeddings), reference :611
-        t2 = tok.view(B * 128, C)
+        t2 = tok.view(B * T, C)
         pending = None                                           # split-K partial sums of the last fc2, not yet folded into t2
         for blk in self.trans_blocks:
-            pending = blk(t2, dtype, pending)
+            pending = blk(t2, dtype, pending, ntok=T)
         if pending is not None:
-            tok_f = ops.layernorm_reduce(t2, pending, lnf_w, lnf_b, torch.float32, self.ln_f.eps).view(B, 128, C)
+            tok_f = ops.layernorm_reduce(t2, pending, lnf_w, lnf_b, torch.float32, self.ln_f.eps).view(B, T, C)
         else:
-            tok_f = ops.layernorm(t2, lnf_w, lnf_b, torch.float32, self.ln_f.eps).view(B, 128, C)
-        return PendingBilinear(tok_f, 0, H, W, dtype), PendingBilinear(tok_f, 1, H, W, dtype)
+            tok_f = ops.layernorm(t2, lnf_w, lnf_b, torch.float32, self.ln_f.eps).view(B, T, C)
+        tok_f.anchor_grid = grid                                 # ops.token_grid: the consumers (Model's fused dual de-tokeniser) read it
+        return PendingBilinear(tok_f, 0, H, W, dtype, grid), PendingBilinear(tok_f, 1, H, W, dtype, grid)
 
 
 # ------------------------------------------------------------------------------ names outside the hot path

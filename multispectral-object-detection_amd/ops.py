@@ -566,18 +566,42 @@ def add(a, b, out=None):
     return out
 
 
-def gpt_tokenize(rgb, ir, pos_emb):
-    """-> float32 tokens [B,128,C]."""
+ANCHOR_GRID = (8, 8)      # the reference's default GPT grid: the kernels of the 8x8 path (cft_gpt_tokenize, cft_attention, ...)
+
+
+def token_grid(tokens, grid=None):
+    """The anchor grid (va, ha) of a GPT token tensor [B, 2*va*ha, C]: ``grid`` when given, else the ``anchor_grid`` attribute that
+    ``GPT.forward`` sets on the tokens it hands to its consumers, else the 8 x 8 default.  (The token count alone does not fix the grid:
+    4 x 16 and 8 x 8 both have 128 tokens.)"""
+    return tuple(grid) if grid is not None else getattr(tokens, "anchor_grid", ANCHOR_GRID)
+
+
+def _grid(grid):
+    va, ha = (int(g) for g in grid)
+    if va < 1 or ha < 1 or va * ha > 1024:
+        raise NotImplementedError(f"anchor grid {va}x{ha}: supported grids have 1 <= vert_anchors, horz_anchors and "
+                                  f"vert_anchors * horz_anchors <= 1024 (T = 2 * va * ha <= 2048 tokens)")
+    return va, ha
+
+
+def gpt_tokenize(rgb, ir, pos_emb, grid=ANCHOR_GRID):
+    """-> float32 tokens [B, 2*va*ha, C] (adaptive average pool of both streams to the ``grid`` = (va, ha) anchors, + pos_emb)."""
     _require_cuda(rgb, "gpt_tokenize")
+    va, ha = _grid(grid)
     rgb, ld_r = as_nhwc(rgb)
     ir, ld_i = as_nhwc(ir)
     B, C, H, W = rgb.shape
-    tokens = torch.empty((B, 128, C), dtype=torch.float32, device=rgb.device)
+    T = 2 * va * ha
+    tokens = torch.empty((B, T, C), dtype=torch.float32, device=rgb.device)
     lib = _lib.load()
-    st = _timed("cft_tokenize", 0.0, 2.0 * B * H * W * C * rgb.element_size() + B * 128 * C * 4,
-                lambda: lib.cft_gpt_tokenize(rgb.data_ptr(), ld_r, 0, ir.data_ptr(), ld_i, 0, pos_emb.data_ptr(), tokens.data_ptr(),
-                                             B, H, W, C, _dt(rgb.dtype), _stream()))
-    _lib.check(st, "cft_gpt_tokenize")
+    if (va, ha) == (8, 8):
+        fn = lambda: lib.cft_gpt_tokenize(rgb.data_ptr(), ld_r, 0, ir.data_ptr(), ld_i, 0, pos_emb.data_ptr(), tokens.data_ptr(),  # noqa: E731
+                                          B, H, W, C, _dt(rgb.dtype), _stream())
+    else:
+        fn = lambda: lib.cft_gpt_tokenize_grid(rgb.data_ptr(), ld_r, 0, ir.data_ptr(), ld_i, 0, pos_emb.data_ptr(), tokens.data_ptr(),  # noqa: E731
+                                               B, H, W, C, va, ha, _dt(rgb.dtype), _stream())
+    st = _timed("cft_tokenize", 0.0, 2.0 * B * H * W * C * rgb.element_size() + B * T * C * 4, fn)
+    _lib.check(st, "cft_gpt_tokenize" if (va, ha) == (8, 8) else "cft_gpt_tokenize_grid")
     return tokens
 
 
@@ -593,21 +617,36 @@ def layernorm(x, gamma, beta, out_dtype, eps=1e-5):
     return out
 
 
-def attention(qkv, B, heads, dk, dkp, pdrop=0.0):
-    """``pdrop`` > 0: training-mode dropout of the attention probabilities inside the kernel."""
+def attention(qkv, B, heads, dk, dkp, pdrop=0.0, T=128, general=False):
+    """qkv [B*T, 3*heads*dkp] -> [B*T, heads*dkp].  ``pdrop`` > 0: training-mode dropout of the attention probabilities inside the
+    kernel.  T = 128 runs the single-tile kernel (cft_attention), any other T (1 .. 2048) the flash-style one (cft_attention_tokens);
+    ``general=True`` forces the latter at T = 128 too."""
     _require_cuda(qkv, "attention")
-    out = torch.empty((B * 128, heads * dkp), dtype=qkv.dtype, device=qkv.device)
+    out = torch.empty((B * T, heads * dkp), dtype=qkv.dtype, device=qkv.device)
     lib = _lib.load()
     seed = next_dropout_seed() if pdrop > 0 else 0
-    st = _timed("cft_attention", 4.0 * 128 * 128 * dk * heads * B, 4.0 * B * 128 * heads * dkp * qkv.element_size(),
-                lambda: lib.cft_attention(qkv.data_ptr(), out.data_ptr(), B, heads, dk, dkp, _dt(qkv.dtype), float(pdrop), seed, _stream()))
-    _lib.check(st, "cft_attention")
+    flops, abytes = 4.0 * T * T * dk * heads * B, 4.0 * B * T * heads * dkp * qkv.element_size()
+    if T == 128 and not general:
+        st = _timed("cft_attention", flops, abytes,
+                    lambda: lib.cft_attention(qkv.data_ptr(), out.data_ptr(), B, heads, dk, dkp, _dt(qkv.dtype), float(pdrop), seed, _stream()))
+        _lib.check(st, "cft_attention")
+    else:
+        st = _timed("cft_attention_tokens", flops, abytes,
+                    lambda: lib.cft_attention_tokens(qkv.data_ptr(), out.data_ptr(), B, T, heads, dk, dkp, _dt(qkv.dtype), float(pdrop), seed,
+                                                     _stream()))
+        _lib.check(st, "cft_attention_tokens")
     return out
 
 
-def gpt_upsample_add(tokens, s, base, H, W, dtype):
-    """bilinear(8x8 -> HxW) of stream ``s`` of ``tokens`` [B,128,C] (+ base) -> NHWC [B,C,H,W]."""
+def gpt_upsample_add(tokens, s, base, H, W, dtype, grid=None):
+    """bilinear(va x ha -> HxW) of stream ``s`` of ``tokens`` [B, 2*va*ha, C] (+ base) -> NHWC [B,C,H,W]; ``grid`` = (va, ha), by default
+    ``token_grid(tokens)``."""
     _require_cuda(tokens, "gpt_upsample_add")
+    grid = token_grid(tokens, grid)
+    va, ha = _grid(grid)
+    if (va, ha) != (8, 8) and not gpt_dual_tokens_ok(tokens, grid):
+        raise ValueError(f"gpt_upsample_add: tokens must be a contiguous, 16-byte aligned fp32 [B, {2 * va * ha}, C] tensor (C % 4 == 0), "
+                         f"got {tuple(tokens.shape)} {tokens.dtype}")
     B, T, C = tokens.shape
     out = new_nhwc(B, H, W, C, dtype, tokens.device)
     bp, ldb = None, 0
@@ -617,27 +656,34 @@ def gpt_upsample_add(tokens, s, base, H, W, dtype):
             raise ValueError("gpt_upsample_add: base shape/dtype mismatch")
         bp = base.data_ptr()
     lib = _lib.load()
-    st = _timed("cft_upsample_add", 0.0, (2.0 if bp else 1.0) * B * H * W * C * out.element_size(),
-                lambda: lib.cft_gpt_upsample_add(tokens.data_ptr(), s, bp, ldb, 0, out.data_ptr(), C, 0, B, H, W, C, _dt(dtype), _stream()))
-    _lib.check(st, "cft_gpt_upsample_add")
+    if (va, ha) == (8, 8):
+        fn = lambda: lib.cft_gpt_upsample_add(tokens.data_ptr(), s, bp, ldb, 0, out.data_ptr(), C, 0, B, H, W, C, _dt(dtype), _stream())  # noqa: E731
+    else:
+        fn = lambda: lib.cft_gpt_upsample_add_grid(tokens.data_ptr(), s, bp, ldb, 0, out.data_ptr(), C, 0, B, H, W, C, va, ha,  # noqa: E731
+                                                   _dt(dtype), _stream())
+    st = _timed("cft_upsample_add", 0.0, (2.0 if bp else 1.0) * B * H * W * C * out.element_size(), fn)
+    _lib.check(st, "cft_gpt_upsample_add" if (va, ha) == (8, 8) else "cft_gpt_upsample_add_grid")
     return out
 
 
-def gpt_dual_tokens_ok(tokens):
-    """What ``cft_gpt_upsample_add2`` hard-codes about its token tensor: [B, 128, C] (two streams x 8 x 8 anchors), fp32, contiguous,
-    C a multiple of 4 and a 16-byte aligned base (it reads rows as float4 at ``b * 128 + s * 64``)."""
-    return (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dim() == 3 and tokens.shape[1] == 128
+def gpt_dual_tokens_ok(tokens, grid=None):
+    """What ``cft_gpt_upsample_add2`` (and the ``_grid`` de-tokenisers) hard-code about the token tensor: [B, 2*va*ha, C] (two streams x
+    va x ha anchors; 128 at the default 8 x 8), fp32, contiguous, C a multiple of 4 and a 16-byte aligned base (rows are read as float4)."""
+    va, ha = (int(g) for g in token_grid(tokens, grid))
+    return (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dim() == 3 and tokens.shape[1] == 2 * va * ha
             and tokens.dtype == torch.float32 and tokens.is_contiguous() and tokens.shape[2] % 4 == 0 and tokens.data_ptr() % 16 == 0)
 
 
-def gpt_upsample_add_dual(tokens, base0, base1, H, W, dtype, sum_out=None, want_sum=True):
-    """Both streams of a CFT block and the Add behind them in one kernel (cft_gpt_upsample_add2):
-    returns (base0 + up(tokens[:, :64]), base1 + up(tokens[:, 64:]), their sum or None); ``sum_out``: write the sum there
-    (e.g. a channel slice of a planned concat buffer)."""
+def gpt_upsample_add_dual(tokens, base0, base1, H, W, dtype, sum_out=None, want_sum=True, grid=None):
+    """Both streams of a CFT block and the Add behind them in one kernel (cft_gpt_upsample_add2, or cft_gpt_upsample_add2_grid on a
+    ``grid`` other than 8 x 8): returns (base0 + up(tokens[:, :va*ha]), base1 + up(tokens[:, va*ha:]), their sum or None); ``sum_out``:
+    write the sum there (e.g. a channel slice of a planned concat buffer)."""
     _require_cuda(tokens, "gpt_upsample_add_dual")
-    if not gpt_dual_tokens_ok(tokens):
-        raise ValueError(f"gpt_upsample_add_dual: tokens must be a contiguous, 16-byte aligned fp32 [B, 128, C] tensor (C % 4 == 0), got "
-                         f"{tuple(tokens.shape)} {tokens.dtype} (other anchor grids: gpt_upsample_add per stream)")
+    grid = token_grid(tokens, grid)
+    va, ha = _grid(grid)
+    if not gpt_dual_tokens_ok(tokens, grid):
+        raise ValueError(f"gpt_upsample_add_dual: tokens must be a contiguous, 16-byte aligned fp32 [B, {2 * va * ha}, C] tensor (C % 4 == 0), "
+                         f"got {tuple(tokens.shape)} {tokens.dtype}")
     B, T, C = tokens.shape
     base0, ldb0 = as_nhwc(base0)
     base1, ldb1 = as_nhwc(base1)
@@ -657,10 +703,15 @@ def gpt_upsample_add_dual(tokens, base0, base1, H, W, dtype, sum_out=None, want_
     else:
         sum_out = None
     lib = _lib.load()
-    st = _timed("cft_upsample_add", 0.0, (5.0 if want_sum else 4.0) * B * H * W * C * out0.element_size(),
-                lambda: lib.cft_gpt_upsample_add2(tokens.data_ptr(), base0.data_ptr(), ldb0, 0, base1.data_ptr(), ldb1, 0,
-                                                  out0.data_ptr(), C, 0, out1.data_ptr(), C, 0, sp, lds, 0, B, H, W, C, _dt(dtype), _stream()))
-    _lib.check(st, "cft_gpt_upsample_add2")
+    if (va, ha) == (8, 8):
+        fn = lambda: lib.cft_gpt_upsample_add2(tokens.data_ptr(), base0.data_ptr(), ldb0, 0, base1.data_ptr(), ldb1, 0,  # noqa: E731
+                                               out0.data_ptr(), C, 0, out1.data_ptr(), C, 0, sp, lds, 0, B, H, W, C, _dt(dtype), _stream())
+    else:
+        fn = lambda: lib.cft_gpt_upsample_add2_grid(tokens.data_ptr(), base0.data_ptr(), ldb0, 0, base1.data_ptr(), ldb1, 0,  # noqa: E731
+                                                    out0.data_ptr(), C, 0, out1.data_ptr(), C, 0, sp, lds, 0, B, H, W, C, va, ha, _dt(dtype),
+                                                    _stream())
+    st = _timed("cft_upsample_add", 0.0, (5.0 if want_sum else 4.0) * B * H * W * C * out0.element_size(), fn)
+    _lib.check(st, "cft_gpt_upsample_add2" if (va, ha) == (8, 8) else "cft_gpt_upsample_add2_grid")
     return out0, out1, sum_out
 
 
