@@ -2,18 +2,23 @@
 """Headline benchmark: image-pairs/sec, forward only, yolov5l + CFTx3 (FLIR cfg), 640x640, batch 64
 per GPU, bf16 compute (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 A step = one forward of the whole two-stream network over one batch of synthetic pairs already
 resident in HBM (HIP-graph replay of every kernel, pre-NMS detections materialised), followed, for
 N > 1, by the RCCL all-gather of the detections.  Weak scaling: 64 pairs per GPU.  Rank 0 prints
-ONE JSON line; it also carries
+ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints
+the headline (value, ms_per_step, config); --full adds every other leg and check to the line:
+  sustained / single_in_flight / f16   longer, one-at-a-time and fp16 legs of the same step
+  multi_gpu_selfcheck                  collectives proving that every rank took part (N > 1)
   roofline      the dominant kernel family (implicit-GEMM conv/linear, bf16 MFMA): algorithmic
                 FLOPs / summed launch time, each launch bracketed by HIP events on its stream
   cpu_baseline  the CPU oracle (oracle/cft_oracle.py, a port of the reference forward to plain
                 torch fp32) timed on this box's host cores on a bounded sample of the same workload
+  parity_*      the timed batch against the CPU oracle, on the seeded, survey and ladder weights
+                (a miss exits 3)
 """
 import argparse
 import json
@@ -403,6 +408,9 @@ def main():
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the outputs of the last timed step (pred, raw0..2) "
                     "as float32 DIR/<name>.npy; batches larger than 64 MB are sampled by a fixed, seeded subset of pairs (the rows are listed in the line)")
     ap.add_argument("--conv-variant", type=int, default=0, help="A/B runs: cft_set_conv_variant() for the whole process (0 = automatic)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg and check: sustained, single-in-flight and fp16 legs, "
+                    "multi-GPU self-check, roofline, CPU baseline, oracle parity (--no-f16-leg, --no-cpu-baseline, --sustained-steps and "
+                    "--no-parity trim this set); a plain run does none of them")
     args = ap.parse_args()
 
     relaunch = D.launch_command(os.path.abspath(__file__), args.gpus, sys.argv[1:])
@@ -508,24 +516,26 @@ def main():
         log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped['shapes']}")
     local_elapsed = getattr(D.timed_steps, "last_local_elapsed", elapsed)
     n_par = 0 if args.no_parity else min(args.batch, 8)     # the first 8 pairs of the timed batch, at every N (N > 1 lines checked 2)
-    with torch.no_grad():
-        raw_now = step_seq()[1]
-        torch.cuda.synchronize()
-    got_raw = [r[:n_par].float().cpu() for r in raw_now] if n_par else None
+    got_raw = None
+    if args.full:
+        with torch.no_grad():
+            raw_now = step_seq()[1]
+            torch.cuda.synchronize()
+        got_raw = [r[:n_par].float().cpu() for r in raw_now] if n_par else None
     single = None
-    if world == 1 and k_fly > 1:      # the same K steps, one forward at a time
+    if args.full and world == 1 and k_fly > 1:      # the same K steps, one forward at a time
         with torch.no_grad():
             el1 = D.timed_steps(lambda: step_seq()[0], args.steps, args.warmup, sync=torch.cuda.synchronize)
         single = {"value": round(args.batch * args.steps / el1, 2), "unit": "image-pairs/sec", "ms_per_step": round(el1 / args.steps * 1e3, 3),
                   "steps": args.steps, "note": "one forward in flight (each step starts when the previous one has finished)"}
         log(f"single in flight: {single}")
     selfcheck = None
-    if gathering:       # evidence that every rank took part and that the gathered rows are the ranks' own rows
+    if args.full and gathering:       # evidence that every rank took part and that the gathered rows are the ranks' own rows
         selfcheck = D.gather_selfcheck(pred, gather.drain(), rank, world, elapsed_local=local_elapsed, force=args.force_gather)
         if args.force_gather and world == 1:
             selfcheck["note"] = "forced at N = 1: the collectives ran through RCCL with world size 1"
     sustained = None
-    if world == 1 and args.sustained_steps > 0 and not args.no_graph:
+    if args.full and world == 1 and args.sustained_steps > 0 and not args.no_graph:
         probe = None
         try:
             probe = ShaderClockProbe(dev)
@@ -545,9 +555,26 @@ def main():
             sc["bf16_mfma_peak_at_median_clock_tflops"] = round(PEAK_BF16_TFLOPS * sc["s_memtime_mhz"]["median"] / 2400.0, 1)
         log(f"sustained leg: {sustained}")
 
+    ok, line = True, None
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * args.batch * args.steps / elapsed
+        line = {
+            "metric": "image-pairs/sec fwd, yolov5l+CFTx3 640\u00d7640 bs64, 1/2/4/8 GPU",
+            "value": round(value, 2), "unit": "image-pairs/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"{args.config} ({WORKLOADS.get(args.config, args.config)}) two-stream forward, "
+                                   f"{args.size}x{args.size}, {args.batch} pairs/GPU, BN folded, pre-NMS detections",
+                       "pairs_per_gpu": args.batch, "image_size": args.size, "parallelism": f"batch-shard x{world}",
+                       "hip_graph": not args.no_graph, "two_hip_streams": not args.no_overlap and not fly_single, "forwards_in_flight": k_fly,
+                       **({"streams_per_forward_in_flight": 1, "single_in_flight_streams": 2} if fly_single else {}), "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
+                       **({"stream_group_probe_ms_per_step": stream_probe_ms} if stream_probe_ms else {}),
+                       **({"depth_first": args.depth_first} if args.depth_first else {}), **({"stream_priorities": args.stream_priorities} if args.stream_priorities else {}),
+                       **({"conv_variant": args.conv_variant} if args.conv_variant else {})},
+            **({"dump_outputs": dumped} if dumped else {}),
+        }
+    if rank == 0 and args.full:
         n_launch, flops, secs, fam, ovh, abytes, aux = gemm_family_time(model, rgb, ir)
         log(f"gemm family: {n_launch} launches, {secs * 1e3:.2f} ms, {flops / secs / 1e12:.1f} TFLOP/s")
         top = sorted(fam.items(), key=lambda kv: -kv[1][2])[:6]
@@ -604,20 +631,7 @@ def main():
                                     "max_frac_with_this_decomposition_if_they_add": round(cft_mfma_ms / (cft_mfma_ms + cft_hbm_ms), 4)},
                          "launches": sum(v[0] for k, v in fam.items() if k.startswith("linear")) + sum(v[0] for v in aux.values()),
                          "parts_ms": {"linears": lin["ms"], **{k[4:]: round(v[2] * 1e3, 3) for k, v in aux.items()}}}
-        line = {
-            "metric": "image-pairs/sec fwd, yolov5l+CFTx3 640\u00d7640 bs64, 1/2/4/8 GPU",
-            "value": round(value, 2), "unit": "image-pairs/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"{args.config} ({WORKLOADS.get(args.config, args.config)}) two-stream forward, "
-                                   f"{args.size}x{args.size}, {args.batch} pairs/GPU, BN folded, pre-NMS detections",
-                       "pairs_per_gpu": args.batch, "image_size": args.size, "parallelism": f"batch-shard x{world}",
-                       "hip_graph": not args.no_graph, "two_hip_streams": not args.no_overlap and not fly_single, "forwards_in_flight": k_fly,
-                       **({"streams_per_forward_in_flight": 1, "single_in_flight_streams": 2} if fly_single else {}), "env": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
-                       **({"stream_group_probe_ms_per_step": stream_probe_ms} if stream_probe_ms else {}),
-                       **({"depth_first": args.depth_first} if args.depth_first else {}), **({"stream_priorities": args.stream_priorities} if args.stream_priorities else {}),
-                       **({"conv_variant": args.conv_variant} if args.conv_variant else {})},
-            **({"dump_outputs": dumped} if dumped else {}),
+        line.update({
             "sustained": sustained, "single_in_flight": single, "multi_gpu_selfcheck": selfcheck,
             "roofline": {"bound": "mfma", "kernel": "conv_gemm_kernel (implicit-GEMM conv/linear family; incl. the dedicated Focus kernel and the fused 64- / 128-channel Bottleneck kernels: 2 + 27 launches of the cfg3 forward)",
                          "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
@@ -635,7 +649,7 @@ def main():
                          "worst_shapes_vs_own_floors": [{"shape": k, "launches": r["launches"], "us_per_launch": r["us_per_launch"], "mfma_us": r["mfma_us"],
                                                          "hbm_us": r["hbm_us"], "measured_over_mfma_plus_hbm": r["measured_over_mfma_plus_hbm"],
                                                          "excess_ms": r["excess_ms"]} for k, r in worst]},
-        }
+        })
         # Both floors of the whole step: the matrix floor at the dense peak and the HBM floor on the step's own bytes
         # (algorithmic = every logged kernel's inputs once + outputs once; counters = the PMC profile of the same configuration).  The
         # larger one binds: for cfg3 at 64 pairs that is HBM, although 99.6 % of the FLOPs are MFMA work.
@@ -688,7 +702,6 @@ def main():
         if not args.no_cpu_baseline and world == 1:   # the CPU leg is reported at N = 1 only
             nb = max(1, min(args.batch, 8))
             (_, want_raw), line["cpu_baseline"] = cpu_baseline(cfg, sd_cpu, rgb[:nb].cpu(), ir[:nb].cpu())
-        ok = True
         if n_par:
             from oracle.cft_oracle import OracleModel
             from oracle.lowp_oracle import AutocastOracle
@@ -734,6 +747,7 @@ def main():
                 if lp["meets_north_star_bound"]:
                     line["parity_green_dtype_ladder"] = args.dtype
                 log(f"ladder-rung parity: {lp}")
+    if rank == 0:
         print(json.dumps(line), flush=True)
         if not ok:
             log("PARITY FAILURE at the benchmarked shape - see parity_at_bench_shape in the line above")

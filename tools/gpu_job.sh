@@ -9,7 +9,7 @@ case $JOB in
   parity)      # the round-3 parity tests + the bench line with parity_at_bench_shape / sustained
     timeout 1500 python -m pytest tests -q -m gpu -x -k "references_own_bf16 or reference_constructor or benchmarked or cfg5_bf16 or channel_slices_of_a_six or fresh_model or train_forward or profile_flag" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt
     tail -5 $O/tests.log
-    timeout 900 python bench.py > $O/bench.json 2> $O/bench.log; echo "bench rc=$?" | tee -a $O/summary.txt
+    timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.log; echo "bench rc=$?" | tee -a $O/summary.txt
     tail -3 $O/bench.log; head -c 600 $O/bench.json ;;
   tests)       # full -m gpu suite + smoke
     timeout 2400 python -m pytest tests -q -m gpu -x --durations=40 "$@" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt
@@ -23,13 +23,13 @@ case $JOB in
     tail -4 $O/tests.log
     timeout 900 python tools/gemm_bench.py --variants 900,0 --out $JOB/gemm.json > $O/gemm.log 2>&1; echo "gemm rc=$?" | tee -a $O/summary.txt
     grep -E "^variant|^best" $O/gemm.log
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     for v in 900 0 900 0; do timeout 300 python bench.py $X --conv-variant $v > $O/bench_v$v.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/bench_v$v.json'));print('variant $v', d['value'], d['ms_per_step'], d['roofline']['frac'])" | tee -a $O/summary.txt; done ;;
   batches)     # pairs/s against the batch per GPU (tile-count quantisation on 256 CUs: 64 pairs = 400 tiles of 256 rows at 40x40)
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     for b in 64 80 48 96 64 80; do timeout 300 python bench.py $X --batch $b > $O/bench_b$b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/bench_b$b.json'));print('batch $b', d['value'], d['ms_per_step'], d['roofline']['frac'])" | tee -a $O/summary.txt; done ;;
   inflight)    # forwards in flight x intra-forward stream overlap
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     for cfgline in "--in-flight 2" "--in-flight 3" "--in-flight 3 --no-overlap" "--in-flight 4" "--in-flight 2" "--in-flight 3"; do
       timeout 400 python bench.py $X $cfgline > $O/b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/b.json'));print('$cfgline', d['value'], d['ms_per_step'], d.get('single_in_flight'))" | tee -a $O/summary.txt; done ;;
   nms)         # NMS tests + timing on the bench workload
@@ -47,7 +47,7 @@ PY
   diag)        # parity diagnostics (measured errors per configuration / precision, incl. vs the reference's own bf16 forward)
     timeout 900 python tests/gpu_diag.py > $O/diag.log 2>&1; echo "diag rc=$?" | tee $O/summary.txt; cp gpurun_out/diag.json $O/diag.json; grep lowp_case $O/diag.log | cut -c1-400 ;;
   prof1)       # rocprofv3 kernel stats of the single-stream, one-forward-in-flight run (per-kernel durations are meaningful)
-    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof1 --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-f16-leg --no-overlap --in-flight 1 --sustained-steps 0 --no-parity > $O/prof1.log 2>&1; echo "prof single-stream rc=$?" | tee $O/summary.txt
+    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof1 --output-format csv -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-f16-leg --no-overlap --in-flight 1 --sustained-steps 0 --no-parity > $O/prof1.log 2>&1; echo "prof single-stream rc=$?" | tee $O/summary.txt
     cp $(ls $O/prof1/*/*kernel_stats.csv | head -1) $O/bench_bs64_kernel_stats.csv; rm -rf $O/prof1; tail -2 $O/prof1.log | cut -c1-300 ;;
   pmc)         # PMC counters of the 16-wave GEMM kernel on 3x3 256->256 @40 (+res), generic (900) and uniform-K-walk (0) address path
     for v in 900 0; do
@@ -62,7 +62,7 @@ PY
     timeout 1200 python -m pytest tests/test_gpu_ops.py -q -m gpu -x -k "asm_gemm" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -5 $O/tests.log
     timeout 1200 python tools/gemm_bench.py --used --variants ${1:-97,0} --rounds 3 --out $JOB/gemm.json > $O/gemm.log 2>&1; echo "gemm rc=$?" | tee -a $O/summary.txt
     grep -E "^variant|^best|us " $O/gemm.log | tail -80
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     for v in 97 0 97 0; do timeout 300 python bench.py $X --conv-variant $v > $O/bench_v$v.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/bench_v$v.json'));print('variant $v', d['value'], d['ms_per_step'], d['roofline']['frac'], (d.get('single_in_flight') or {}).get('value'))" | tee -a $O/summary.txt; done ;;
   bneck)       # the fused Bottleneck kernels against the two launches + ablation probes (probe build)
     CFT_BENCH_LIB=multispectral-object-detection_amd/libcft_hip_probes.so timeout 600 python tools/bneck_bench.py 128 > $O/bneck128.log 2>&1; echo "bneck128 rc=$?"; cat $O/bneck128.log | tail -12 ;;
@@ -71,7 +71,7 @@ PY
     timeout 600 python tools/bneck_bench.py 128 > $O/bneck128.log 2>&1; echo "bneck128 rc=$?"; cat $O/bneck128.log | tail -8 ;;
   r6b)         # round 6: whole-forward A/B (variant 97 = round-5 choice, 0 = asm kernels) with the board power sampled during the sustained leg
     rocm-smi --showmaxpower --showpower 2>&1 | grep -i -E "power|watt" | head -4 | tee $O/summary.txt
-    X="--no-cpu-baseline --no-f16-leg --no-parity --sustained-steps 400"
+    X="--full --no-cpu-baseline --no-f16-leg --no-parity --sustained-steps 400"
     for v in 97 0 97 0; do
       (timeout 300 python bench.py $X --conv-variant $v > $O/b_$v.json 2>> $O/bench.log &)
       sleep 50; for i in 1 2 3 4 5 6; do cat /sys/class/drm/card*/device/hwmon/hwmon*/power1_input 2>/dev/null | tr '\n' ' '; echo; sleep 1; done | tee -a $O/power_$v.txt   # microwatts, every card of the node (ours is the one that moves)
@@ -95,14 +95,14 @@ PY
   chain6)      # round 6: the chained pairs on the asm K loop (variant 0) against the 16-wave chained kernel (97): tests, per-pair timing, whole forward
     timeout 1500 python -m pytest tests/test_gpu_ops.py tests/test_gpu_model.py -q -m gpu -x -k "chain" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -4 $O/tests.log
     for v in 97 0 97 0; do echo "variant $v"; CFT_CHAIN_BENCH_VARIANT=$v timeout 300 python tools/chain_bench.py --res 2>&1 | tail -3; CFT_CHAIN_BENCH_VARIANT=$v timeout 300 python tools/chain_bench.py 2>&1 | grep -E "256|bf16" | tail -4; done | tee $O/chain_bench.txt
-    X="--no-cpu-baseline --no-f16-leg --no-parity --sustained-steps 0"
+    X="--full --no-cpu-baseline --no-f16-leg --no-parity --sustained-steps 0"
     for v in 97 0 97 0; do timeout 300 python bench.py $X --conv-variant $v > $O/bench_v$v.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/bench_v$v.json'));print('variant $v', d['value'], d['ms_per_step'], d['roofline']['frac'], (d.get('single_in_flight') or {}).get('value'))" | tee -a $O/summary.txt; done ;;
   micro)       # micro-benchmarks: HBM read / write / copy ceilings; Infinity-Cache producer -> consumer; DMA stream coupling; power coupling
     for m in ${@:-hbm_rw mall_probe dma_ring power_coupling}; do timeout 200 tools/micro/$m > $O/$m.txt 2>&1; echo "$m rc=$?"; tail -40 $O/$m.txt; done ;;
   r5a)         # round 5, first call: Infinity-Cache probe; new tests (depth-first prefix, survey weights, ADVICE fixes); depth-first A/B on the forward
     timeout 200 tools/micro/mall_probe > $O/mall_probe.txt 2>&1; echo "mall rc=$?" | tee $O/summary.txt; cat $O/mall_probe.txt
     timeout 1500 python -m pytest tests/test_gpu_model.py tests/test_gpu_ops.py -q -m gpu -x -k "depth_first or survey or chain or cft_output_fusion or profile_flag or upsample_add_dual" > $O/tests.log 2>&1; echo "tests rc=$?" | tee -a $O/summary.txt; tail -5 $O/tests.log
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     run() { tag=$1; shift; timeout 400 python bench.py $X "$@" > $O/b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/b.json'));print('$tag', d['value'], d['ms_per_step'], (d.get('single_in_flight') or {}).get('value'), d['roofline']['whole_step']['frac'], d['config'].get('stream_group_probe_ms_per_step'))" | tee -a $O/summary.txt; }
     run "layer by layer (default)"; cp gpurun_out/bench_families.json $O/families_default.json
     run "depth-first 8 chunks, rows 0-4" --depth-first 8; cp gpurun_out/bench_families.json $O/families_df8.json
@@ -115,7 +115,7 @@ PY
     run "layer by layer, one forward in flight" --in-flight 1 ;;
   r5b)         # round 5: chained 3x3 (+ shortcut) + 1x1 kernel, split-K linears + LayerNorm-reduce: op / model tests, A/B on the forward
     timeout 1500 python -m pytest tests/test_gpu_model.py tests/test_gpu_ops.py -q -m gpu -x -k "chain or splitk or layernorm or attention or cft_output_fusion or graph_replay or train_forward" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -5 $O/tests.log
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     run() { tag=$1; shift; timeout 400 python bench.py $X "$@" > $O/b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/b.json'));r=d['roofline'];print('$tag', d['value'], d['ms_per_step'], (d.get('single_in_flight') or {}).get('value'), r['whole_step']['frac'], r['by_block']['cft_block_whole']['ms'], r['by_block']['cft_block_whole']['frac'], d['config'].get('stream_group_probe_ms_per_step'))" | tee -a $O/summary.txt; }
     run "default (chain + splitk)"; cp gpurun_out/bench_families.json $O/families_default.json
     run "no splitk" --no-splitk; cp gpurun_out/bench_families.json $O/families_nosplitk.json
@@ -127,7 +127,7 @@ PY
     run "bs8 no splitk" --batch 8 --no-splitk ;;
   r5c)         # round 5: the one-kernel stem (Focus + Conv s2 + C3 cv1|cv2): op / model bit-identity tests, A/B on the forward
     timeout 1500 python -m pytest tests/test_gpu_model.py tests/test_gpu_ops.py -q -m gpu -x -k "stem or chain or focus or depth_first or graph_replay or uint8 or six_channel" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -5 $O/tests.log
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     run() { tag=$1; shift; timeout 400 python bench.py $X "$@" > $O/b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/b.json'));r=d['roofline'];print('$tag', d['value'], d['ms_per_step'], (d.get('single_in_flight') or {}).get('value'), r['whole_step']['frac'], r['floors']['algorithmic_gbytes_per_step'], d['config'].get('stream_group_probe_ms_per_step'))" | tee -a $O/summary.txt; }
     run "stem" --stem; cp gpurun_out/bench_families.json $O/families_stem.json
     run "default (Focus, then chained Conv + C3)"; cp gpurun_out/bench_families.json $O/families_default.json
@@ -136,7 +136,7 @@ PY
     timeout 300 python tools/stem_bench.py > $O/stem_bench.txt 2>&1; cat $O/stem_bench.txt ;;
   r5d)         # round 5: small-batch regime after the size heuristics (chained 3x3 + shortcut only from 192 tiles; split-K to >= 128 workgroups)
     timeout 600 python -m pytest tests/test_gpu_model.py tests/test_gpu_ops.py -q -m gpu -x -k "chain_res or c3_chain or splitk" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -3 $O/tests.log
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     run() { tag=$1; shift; timeout 400 python bench.py $X "$@" > $O/b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/b.json'));r=d['roofline'];print('$tag', d['value'], d['ms_per_step'], (d.get('single_in_flight') or {}).get('value'), r['whole_step']['frac'], r['by_block']['cft_block_whole']['ms'], r['by_block']['cft_block_whole']['frac'], r['by_block']['backbone_head_convs']['ms'])" | tee -a $O/summary.txt; }
     run "bs8" --batch 8
     run "bs8 no splitk" --batch 8 --no-splitk
@@ -147,7 +147,7 @@ PY
     run "cfg5 16 pairs 1280" --config cfg5 --batch 16 --size 1280
     run "cfg5 16 pairs 1280 no splitk" --config cfg5 --batch 16 --size 1280 --no-splitk ;;
   knobs)       # runtime-environment knobs on the default step (each leg in its own process; a crash only loses its leg)
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     run() { tag=$1; shift; timeout 300 env "$@" python bench.py $X > $O/b.json 2>> $O/bench.log; rc=$?; python -c "import json;d=json.load(open('$O/b.json'));print('$tag', d['value'], d['ms_per_step'], (d.get('single_in_flight') or {}).get('value'), d['config'].get('stream_group_probe_ms_per_step'))" 2>/dev/null | tee -a $O/summary.txt || echo "$tag FAILED rc=$rc" | tee -a $O/summary.txt; rm -f $O/b.json; }
     run "default" A=1
     run "DEBUG_CLR_GRAPH_PACKET_CAPTURE=1" DEBUG_CLR_GRAPH_PACKET_CAPTURE=1
@@ -168,22 +168,22 @@ PY
     bash tools/pmc_traffic.sh $O/traffic > $O/traffic.log 2>&1
     python tools/traffic_summary.py $O/traffic $O/traffic.json config=cfg3 batch=64 size=640 dtype=bf16 | tee $O/summary.txt
     rm -rf $O/traffic; cp $O/traffic.json profiles/r06_traffic.json
-    timeout 900 python bench.py > $O/bench_bs64.json 2> $O/bench.log; echo "bench rc=$?" | tee -a $O/summary.txt
+    timeout 900 python bench.py --full > $O/bench_bs64.json 2> $O/bench.log; echo "bench rc=$?" | tee -a $O/summary.txt
     cp gpurun_out/bench_families.json $O/gemm_families_cfg3.json
-    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof1 --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-f16-leg --no-overlap --in-flight 1 --sustained-steps 0 --no-parity > $O/prof1.log 2>&1; echo "prof single-stream rc=$?" | tee -a $O/summary.txt
+    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof1 --output-format csv -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-f16-leg --no-overlap --in-flight 1 --sustained-steps 0 --no-parity > $O/prof1.log 2>&1; echo "prof single-stream rc=$?" | tee -a $O/summary.txt
     cp $(ls $O/prof1/*/*kernel_stats.csv | head -1) $O/bench_bs64_kernel_stats.csv; rm -rf $O/prof1
-    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof2 --output-format csv -- python bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity > $O/prof2.log 2>&1; echo "prof two-stream rc=$?" | tee -a $O/summary.txt
+    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof2 --output-format csv -- python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity > $O/prof2.log 2>&1; echo "prof two-stream rc=$?" | tee -a $O/summary.txt
     cp $(ls $O/prof2/*/*kernel_stats.csv | head -1) $O/bench_bs64_kernel_stats_two_streams_40steps.csv; rm -rf $O/prof2
     # the parity-green 16-bit mode with the same evidence as the bf16 line: full line + rocprofv3 kernel stats
-    timeout 900 python bench.py --dtype f16 --no-cpu-baseline > $O/bench_bs64_f16.json 2> $O/bench_f16.log; echo "bench f16 rc=$?" | tee -a $O/summary.txt
+    timeout 900 python bench.py --full --dtype f16 --no-cpu-baseline > $O/bench_bs64_f16.json 2> $O/bench_f16.log; echo "bench f16 rc=$?" | tee -a $O/summary.txt
     cp gpurun_out/bench_families.json $O/gemm_families_cfg3_f16.json
-    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof3 --output-format csv -- python bench.py --dtype f16 --steps 20 --warmup 3 --no-cpu-baseline --no-overlap --in-flight 1 --sustained-steps 0 --no-parity > $O/prof3.log 2>&1; echo "prof f16 single-stream rc=$?" | tee -a $O/summary.txt
+    timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof3 --output-format csv -- python bench.py --full --dtype f16 --steps 20 --warmup 3 --no-cpu-baseline --no-overlap --in-flight 1 --sustained-steps 0 --no-parity > $O/prof3.log 2>&1; echo "prof f16 single-stream rc=$?" | tee -a $O/summary.txt
     cp $(ls $O/prof3/*/*kernel_stats.csv | head -1) $O/bench_bs64_f16_kernel_stats.csv; rm -rf $O/prof3
     head -c 1500 $O/bench_bs64.json ;;
   configs)     # bench lines of the other BASELINE configurations (single-GPU share)
-    X="--no-cpu-baseline --no-f16-leg --sustained-steps 0"
+    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0"
     timeout 300 python bench.py --batch 8 $X > $O/bench_bs8.json 2> $O/bs8.log; echo "bs8 rc=$?"
-    timeout 300 python bench.py --config cfg2 --batch 16 --dtype f32 --no-cpu-baseline --sustained-steps 0 > $O/bench_cfg2.json 2> $O/cfg2.log; echo "cfg2 rc=$?"
+    timeout 300 python bench.py --full --config cfg2 --batch 16 --dtype f32 --no-cpu-baseline --sustained-steps 0 > $O/bench_cfg2.json 2> $O/cfg2.log; echo "cfg2 rc=$?"
     timeout 300 python bench.py --config cfg4 --batch 64 $X > $O/bench_cfg4.json 2> $O/cfg4.log; echo "cfg4 rc=$?"
     timeout 400 python bench.py --config cfg5 --batch 16 --size 1280 $X > $O/bench_cfg5.json 2> $O/cfg5.log; echo "cfg5 rc=$?"
     python - <<'PY'
