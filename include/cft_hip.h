@@ -328,6 +328,44 @@ int cft_nms(const float* pred, int B, int rows, int no, float conf_thres, float 
             int agnostic, int multi_label, const unsigned char* class_allow, int max_det, int max_nms,
             void* scratch, long scratch_bytes, float* dets, int* counts, void* stream);
 
+/*
+ * mAP statistics of test.py on the GPU.
+ *
+ * cft_eval_match replaces the per-image loop of test.py:132-218 (labels to pixels :125, xywh2xyxy + scale_coords of the
+ * labels :201-202 and of the predictions :148-149, box_iou :207 and the greedy per-class matching :204-218).  Two launches:
+ * a stable grouping of the labels by image, then one workgroup per image.
+ *   dets [B, max_det, 6] / counts [B] : the cft_nms output (device; never read on the host)
+ *   targets [nt, 6]                   : image index, class, x, y, w, h normalised to the img_h x img_w letterbox (device)
+ *   geom [B, 5]                       : h0, w0, gain, padw, padh per image, float32 (device; scale_coords, utils/general.py:353-366)
+ *   iouv_host [niou]                  : the IoU thresholds, HOST memory, copied into the launch (niou <= 16)
+ * Writes, per slot (b, r) of [B, max_det]: tp_bits (bit k = correct[:, k]), conf (or NULL), pcls (int class, 0 if single_cls,
+ * -1 for r >= counts[b]; or NULL) and optionally correct [B, max_det, niou] bytes.  label_hist (int [nc + 1], or NULL) is ADDED
+ * to: per-class label counts, slot nc = labels whose class is not an integer in [0, nc).  tcls [nt] / nl [B] (or NULL) receive
+ * the label classes grouped by image in target order and the label count of each image.
+ * workspace: >= cft_eval_match_workspace_bytes(B, nt) bytes, 256-byte aligned.  No allocation, no synchronisation.
+ */
+long cft_eval_match_workspace_bytes(int B, int nt);
+int cft_eval_match(const float* dets, const int* counts, int B, int max_det, const float* targets, int nt, int img_h, int img_w,
+                   const float* geom, const float* iouv_host, int niou, int single_cls, void* workspace, long workspace_bytes,
+                   unsigned char* correct, unsigned short* tp_bits, float* conf, int* pcls, int* label_hist, int nc,
+                   int* tcls, int* nl, void* stream);
+
+/*
+ * cft_eval_ap replaces ap_per_class (utils/metrics.py:18-79) and compute_ap (:82-108) over n accumulated detections:
+ * a stable LSD radix sort by (class, conf descending; ties in insertion order), exact integer TP / FP counts, recall and
+ * precision in float64, p / r at the 1000 px points and the 101-point interpolated AP with numpy's np.interp rule, f1 and
+ * the argmax of its class mean.  Classes are those with label_hist[c] > 0 (np.unique(target_cls)); detections of other
+ * classes (or pcls outside [0, nc)) are dropped.
+ *   tp_bits [n] (bit k = IoU column k), conf [n] float, pcls [n] int, label_hist [nc] int  (device)
+ *   px [1000], x [101] : the float64 grids np.linspace(0, 1, 1000) and np.linspace(0, 1, 101) (device)
+ *   out [nc * (4 + niou)] float64 (device) = p[nc] | r[nc] | f1[nc] | ntp[nc] (TPs in column 0) | ap[nc, niou];
+ *   rows of classes without labels are 0.
+ * workspace: >= cft_eval_ap_workspace_bytes(n, nc) bytes, 256-byte aligned.  No allocation, no synchronisation.
+ */
+long cft_eval_ap_workspace_bytes(long n, int nc);
+int cft_eval_ap(const unsigned short* tp_bits, const float* conf, const int* pcls, long n, int niou, const int* label_hist, int nc,
+                const double* px, const double* x, void* workspace, long workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,12 +15,12 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: experiments with an alternative build, e.g. the probe library)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip")
+SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip")
 
 HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "conv_gemm_asm.inc")
 
 CFT_BF16, CFT_F32, CFT_F16 = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 
 _c = ctypes
@@ -62,6 +62,10 @@ SIGNATURES = {
     "cft_gpt_upsample_add2_grid": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "cft_nms": [_vp, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _i, _vp, _l, _vp, _vp, _vp],
     "cft_detect_decode": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _l, _l, _vp],
+    "cft_eval_match_workspace_bytes": [_i, _i],      # returns long (bytes)
+    "cft_eval_match": [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "cft_eval_ap_workspace_bytes": [_l, _i],         # returns long (bytes)
+    "cft_eval_ap": [_vp, _vp, _vp, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp],
 }
 
 _lib = None
@@ -118,6 +122,8 @@ def load():
     lib.cft_last_error.argtypes = []
     lib.cft_last_error.restype = ctypes.c_char_p
     lib.cft_batchnorm_train_workspace.restype = ctypes.c_long
+    lib.cft_eval_match_workspace_bytes.restype = ctypes.c_long
+    lib.cft_eval_ap_workspace_bytes.restype = ctypes.c_long
     _lib = lib
     return lib
 

@@ -1,0 +1,316 @@
+"""mAP statistics of the reference's ``test.py`` on the GPU (the step after batched NMS).
+
+The reference walks images, then classes, in Python (``test.py:132-218``: ``nonzero()`` and one ``.item()`` per
+matched detection) and then runs ``ap_per_class`` (``utils/metrics.py:18-108``) in numpy.  Here both are HIP kernels
+(``csrc/metrics.hip``):
+
+* ``match_batch``          one batch's ``batched_nms`` output against its labels (``cft_eval_match``);
+* ``ap_per_class``         the reference's function, same signature and return value (``cft_eval_ap``);
+* ``DetectionEvaluator``   accumulates batches on the device without host synchronisation and computes
+                           ``test.py``'s metrics with one synchronisation.
+
+Every rule is the reference's: float32 box arithmetic as ATen does it, float64 curves as numpy does them.
+"""
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..ops import _require_cuda, _stream
+
+IOUV = torch.linspace(0.5, 0.95, 10)         # test.py:76, built on the host in float32 as there
+NIOU = IOUV.numel()
+PX = np.linspace(0, 1, 1000)                 # utils/metrics.py:40
+XG = np.linspace(0, 1, 101)                  # utils/metrics.py:97
+
+_grid_cache = {}
+
+
+def _to_device(t, device):
+    """Host tensor -> device without a blocking copy (pinned staging): keeps update() free of host synchronisation."""
+    if t.device == device:
+        return t
+    if t.device.type != "cpu":
+        return t.to(device)
+    return t.contiguous().pin_memory().to(device, non_blocking=True)
+
+
+def _grids(device):
+    g = _grid_cache.get(device)
+    if g is None:
+        g = _grid_cache[device] = (_to_device(torch.from_numpy(PX), device), _to_device(torch.from_numpy(XG), device))
+    return g
+
+
+def geometry(shapes, img_hw):
+    """Per-image float32 [h0, w0, gain, padw, padh] of scale_coords (reference utils/general.py:353-366), from test.py's
+    ``shapes[si] = ((h0, w0), ratio_pad)``.  ratio_pad None: gain and pad from the shapes, in double, as the reference."""
+    H, W = int(img_hw[0]), int(img_hw[1])
+    g = np.empty((len(shapes), 5), np.float64)
+    for i, s in enumerate(shapes):
+        (h0, w0), rp = s[0], s[1] if len(s) > 1 else None
+        h0, w0 = float(h0), float(w0)
+        if rp is None:
+            gain = min(H / h0, W / w0)
+            pad = (W - w0 * gain) / 2, (H - h0 * gain) / 2
+        else:
+            gain = float(rp[0][0])
+            pad = float(rp[1][0]), float(rp[1][1])
+        g[i] = (h0, w0, gain, pad[0], pad[1])
+    return torch.from_numpy(g.astype(np.float32))      # ATen rounds the Python scalars to float32
+
+
+def _pack_dets(dets, counts, device):
+    """(dets [B, max_det, 6], counts [B]) or the list form of non_max_suppression -> device tensors, no host sync."""
+    if isinstance(dets, (list, tuple)):
+        if counts is not None:
+            raise ValueError("match: give counts only with a dets tensor, not with the list form")
+        if len(dets) == 0:
+            raise ValueError("match: empty batch")
+        ns = [int(d.shape[0]) for d in dets]
+        packed = torch.zeros((len(dets), max(1, max(ns)), 6), dtype=torch.float32, device=device)
+        for i, d in enumerate(dets):
+            if d.dim() != 2 or d.shape[1] != 6:
+                raise ValueError(f"match: detections of image {i} must be [n, 6], got {tuple(d.shape)}")
+            if ns[i]:
+                packed[i, :ns[i]].copy_(d)
+        return packed, _to_device(torch.tensor(ns, dtype=torch.int32), device)
+    if not isinstance(dets, torch.Tensor) or dets.dim() != 3 or dets.shape[2] != 6 or dets.shape[0] == 0 or dets.shape[1] == 0:
+        raise ValueError(f"match: dets must be a [B, max_det, 6] tensor with B, max_det >= 1, got {getattr(dets, 'shape', type(dets))}")
+    if counts is None or not isinstance(counts, torch.Tensor) or counts.shape != (dets.shape[0],):
+        raise ValueError("match: counts must be a [B] tensor (the batched_nms output)")
+    _require_cuda(dets, "match_batch")
+    _require_cuda(counts, "match_batch")
+    if dets.dtype != torch.float32 or not dets.is_contiguous():
+        raise ValueError("match: dets must be contiguous float32 (the batched_nms output)")
+    return dets, counts.to(torch.int32).contiguous()
+
+
+@dataclass
+class MatchResult:
+    """Device tensors of one batch, slot (b, r) = detection r of image b (rows r >= counts[b] are empty: pred_cls -1)."""
+    correct: torch.Tensor      # bool [B, max_det, niou]
+    conf: torch.Tensor         # float32 [B, max_det]
+    pred_cls: torch.Tensor     # int32 [B, max_det]
+    counts: torch.Tensor       # int32 [B]
+    tcls: torch.Tensor         # int32 [nt], label classes grouped by image in target order
+    nl: torch.Tensor           # int32 [B], labels per image
+
+    def to_stats(self):
+        """test.py's ``stats`` entries of the batch (:140-143, :221): (correct, conf, pred_cls, tcls) per image, in image order,
+        skipping images without detections and labels.  Copies to the host (synchronises)."""
+        correct, conf, pcls = self.correct.cpu(), self.conf.cpu(), self.pred_cls.cpu()
+        counts, nl, tcls = self.counts.cpu().tolist(), self.nl.cpu().tolist(), self.tcls.cpu().tolist()
+        stats, l0 = [], 0
+        for b, (n, m) in enumerate(zip(counts, nl)):
+            tc = [float(c) for c in tcls[l0:l0 + m]]
+            l0 += m
+            if n == 0:
+                if m:
+                    stats.append((torch.zeros(0, correct.shape[2], dtype=torch.bool), torch.Tensor(), torch.Tensor(), tc))
+                continue
+            stats.append((correct[b, :n], conf[b, :n], pcls[b, :n].float(), tc))
+        return stats
+
+
+def _match(dets, counts, targets, img_hw, shapes, single_cls, tp_bits, conf, pcls, correct, label_hist, nc, tcls, nl):
+    B, max_det = dets.shape[0], dets.shape[1]
+    device = dets.device
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.shape[1] != 6:
+        raise ValueError(f"match: targets must be an [nt, 6] tensor (image, class, x, y, w, h), got {getattr(targets, 'shape', type(targets))}")
+    if len(shapes) != B:
+        raise ValueError(f"match: {len(shapes)} shapes for a batch of {B} images")
+    H, W = int(img_hw[0]), int(img_hw[1])
+    if H <= 0 or W <= 0:
+        raise ValueError(f"match: bad image size {img_hw}")
+    targets = _to_device(targets.float(), device).contiguous()
+    geom = _to_device(geometry(shapes, img_hw), device)
+    nt = targets.shape[0]
+    lib = _lib.load()
+    ws = torch.empty((lib.cft_eval_match_workspace_bytes(B, nt),), dtype=torch.uint8, device=device)
+    iouv = np.ascontiguousarray(IOUV.numpy(), dtype=np.float32)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    st = lib.cft_eval_match(dets.data_ptr(), counts.data_ptr(), B, max_det, ptr(targets) if nt else None, nt, H, W, geom.data_ptr(),
+                            iouv.ctypes.data, NIOU, int(bool(single_cls)), ws.data_ptr(), ws.numel(), ptr(correct), tp_bits.data_ptr(),
+                            ptr(conf), ptr(pcls), ptr(label_hist), int(nc), ptr(tcls), ptr(nl), _stream())
+    _lib.check(st, "cft_eval_match")
+
+
+def match_batch(dets, counts, targets, img_hw, shapes, single_cls=False, out=None):
+    """Match one batch's detections to its labels on the GPU (test.py:132-218).
+
+    dets, counts: the ``batched_nms`` output (or ``non_max_suppression``'s list, with counts=None); targets [nt, 6] as the
+    dataloader yields them (normalised xywh); img_hw = the letterboxed (height, width); shapes = the dataloader's shapes.
+    Returns a ``MatchResult``; ``.to_stats()`` gives test.py's per-image ``stats`` entries.  ``out`` (optional) is a
+    ``MatchResult`` whose tensors are written instead of fresh ones."""
+    device = dets[0].device if isinstance(dets, (list, tuple)) and len(dets) else getattr(dets, "device", None)
+    if device is None or device.type != "cuda":
+        raise RuntimeError("match_batch: detections must be on the GPU (this package has no CPU path)")
+    dets, counts = _pack_dets(dets, counts, device)
+    B, max_det = dets.shape[0], dets.shape[1]
+    nt = targets.shape[0] if isinstance(targets, torch.Tensor) else 0
+    if out is None:
+        out = MatchResult(torch.empty((B, max_det, NIOU), dtype=torch.bool, device=device),
+                          torch.empty((B, max_det), dtype=torch.float32, device=device),
+                          torch.empty((B, max_det), dtype=torch.int32, device=device), counts,
+                          torch.empty((max(nt, 1),), dtype=torch.int32, device=device)[:nt],
+                          torch.empty((B,), dtype=torch.int32, device=device))
+    else:
+        out.counts = counts
+    tp_bits = torch.empty((B, max_det), dtype=torch.int16, device=device)
+    _match(dets, counts, targets, img_hw, shapes, single_cls, tp_bits, out.conf, out.pred_cls, out.correct.view(torch.uint8), None, 0,
+           out.tcls if nt else None, out.nl)
+    return out
+
+
+def _ap_device(tp_bits, conf, pcls, n, niou, hist, nc, device):
+    """cft_eval_ap on device buffers -> device float64 [nc * (4 + niou)] = p | r | f1 | ntp | ap[nc, niou]."""
+    lib = _lib.load()
+    px, xg = _grids(device)
+    ws = torch.empty((lib.cft_eval_ap_workspace_bytes(n, nc),), dtype=torch.uint8, device=device)
+    out = torch.empty((nc * (4 + niou),), dtype=torch.float64, device=device)
+    ptr = lambda t: t.data_ptr() if n else None  # noqa: E731
+    st = lib.cft_eval_ap(ptr(tp_bits), ptr(conf), ptr(pcls), n, niou, hist.data_ptr(), nc, px.data_ptr(), xg.data_ptr(), ws.data_ptr(),
+                         ws.numel(), out.data_ptr(), _stream())
+    _lib.check(st, "cft_eval_ap")
+    return out
+
+
+def _split(out, nc, niou):
+    return out[:nc], out[nc:2 * nc], out[2 * nc:3 * nc], out[3 * nc:4 * nc], out[4 * nc:].reshape(nc, niou)
+
+
+def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, save_dir='.', names=()):
+    """The reference's ap_per_class (utils/metrics.py:18-79) on the GPU: returns numpy (p, r, ap, f1, ap_class).
+
+    tp [n, niou] bool, conf [n], pred_cls [n], target_cls [nl] (numpy arrays or tensors).  Classes must be non-negative integers.
+    Ties in conf keep their input order (numpy's argsort leaves them unspecified); conf is taken in float32 as test.py hands it."""
+    if plot:
+        raise NotImplementedError("ap_per_class: plotting (PR / F1 / P / R curves) is out of scope of this package")
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+    tp, conf, pred_cls, target_cls = as_np(tp), as_np(conf), as_np(pred_cls), as_np(target_cls)
+    if tp.ndim != 2 or not 1 <= tp.shape[1] <= 16:
+        raise ValueError(f"ap_per_class: tp must be [n, niou] with 1 <= niou <= 16, got {tp.shape}")
+    n, niou = tp.shape
+    if conf.shape != (n,) or pred_cls.shape != (n,):
+        raise ValueError(f"ap_per_class: conf and pred_cls must be [{n}], got {conf.shape} and {pred_cls.shape}")
+    tc = target_cls.astype(np.float64).reshape(-1)
+    if tc.size and (not np.all(tc >= 0) or not np.all(tc == np.floor(tc)) or tc.max() > 65534):
+        raise ValueError("ap_per_class: target classes must be integers in [0, 65534]")
+    if not torch.cuda.is_available():
+        raise RuntimeError("ap_per_class: needs a GPU (this package has no CPU path; oracle/ and the tests hold CPU restatements)")
+    if tc.size == 0:
+        return np.zeros(0), np.zeros(0), np.zeros((0, niou)), np.zeros(0), np.zeros(0, np.int32)
+    nc = int(tc.max()) + 1
+    hist = np.bincount(tc.astype(np.int64), minlength=nc).astype(np.int32)
+    pc = pred_cls.astype(np.float64)
+    ok = (pc >= 0) & (pc < nc) & (pc == np.floor(pc))
+    pci = np.where(ok, pc, -1).astype(np.int32)
+    bits = (tp.astype(bool) * (1 << np.arange(niou))).sum(1).astype(np.uint16).view(np.int16) if n else np.zeros(0, np.int16)
+    device = torch.device("cuda", torch.cuda.current_device())
+    d = lambda a: _to_device(torch.from_numpy(np.ascontiguousarray(a)), device)  # noqa: E731
+    out = _ap_device(d(bits), d(conf.astype(np.float32)), d(pci), n, niou, d(hist), nc, device).cpu().numpy()
+    p, r, f1, _, ap = _split(out, nc, niou)
+    ap_class = np.flatnonzero(hist > 0)
+    return p[ap_class], r[ap_class], ap[ap_class], f1[ap_class], ap_class.astype(np.int32)
+
+
+@dataclass
+class EvalResult:
+    """test.py's metrics (:227-236, :292-294).  p, r, ap, f1, ap_class as ap_per_class returns them; nt = labels per class."""
+    mp: float
+    mr: float
+    map50: float
+    map75: float
+    map: float
+    maps: np.ndarray
+    p: np.ndarray
+    r: np.ndarray
+    ap: np.ndarray
+    f1: np.ndarray
+    ap_class: np.ndarray
+    nt: object
+    seen: int
+
+    def as_test_tuple(self):
+        """test.py's ``((mp, mr, map50, map75, map), maps)`` (without the validation losses)."""
+        return (self.mp, self.mr, self.map50, self.map75, self.map), self.maps
+
+
+class DetectionEvaluator:
+    """Accumulates test.py's statistics on the GPU.  ``update()`` never synchronises with the host: every batch appends its
+    B * max_det slots (empty ones are dropped later), so buffer offsets are known on the host.  ``compute()`` synchronises once."""
+
+    def __init__(self, nc, single_cls=False):
+        if int(nc) < 1 or int(nc) > 65535:
+            raise ValueError(f"DetectionEvaluator: nc must be in [1, 65535], got {nc}")
+        self.nc = int(nc)
+        self.single_cls = bool(single_cls)
+        self.device = None
+        self.reset()
+
+    def reset(self):
+        self.n = 0
+        self.seen = 0
+        self._tp = self._conf = self._pcls = self._hist = None
+
+    def _reserve(self, device, need):
+        if self.device is None or self._hist is None:
+            self.device = device
+            self._hist = torch.zeros((self.nc + 1,), dtype=torch.int32, device=device)
+        elif device != self.device:
+            raise ValueError(f"DetectionEvaluator: batch on {device}, earlier batches on {self.device}")
+        cap = 0 if self._tp is None else self._tp.numel()
+        if need <= cap:
+            return
+        cap = max(need, 2 * cap, 1 << 14)
+        tp = torch.empty((cap,), dtype=torch.int16, device=device)
+        conf = torch.empty((cap,), dtype=torch.float32, device=device)
+        pcls = torch.empty((cap,), dtype=torch.int32, device=device)
+        if self.n:
+            tp[:self.n].copy_(self._tp[:self.n])
+            conf[:self.n].copy_(self._conf[:self.n])
+            pcls[:self.n].copy_(self._pcls[:self.n])
+        self._tp, self._conf, self._pcls = tp, conf, pcls
+
+    def update(self, dets, counts, targets, img_hw, shapes):
+        """Add one batch: (dets, counts) from batched_nms, or non_max_suppression's list with counts=None; targets, img_hw and
+        shapes as for match_batch."""
+        device = dets[0].device if isinstance(dets, (list, tuple)) and len(dets) else getattr(dets, "device", None)
+        if device is None or device.type != "cuda":
+            raise RuntimeError("DetectionEvaluator.update: detections must be on the GPU (this package has no CPU path)")
+        dets, counts = _pack_dets(dets, counts, device)
+        B, max_det = dets.shape[0], dets.shape[1]
+        k = B * max_det
+        self._reserve(device, self.n + k)
+        sl = slice(self.n, self.n + k)
+        _match(dets, counts, targets, img_hw, shapes, self.single_cls, self._tp[sl], self._conf[sl], self._pcls[sl], None,
+               self._hist, self.nc, None, None)
+        self.n += k
+        self.seen += B
+
+    def compute(self):
+        nc, niou = self.nc, NIOU
+        maps0 = np.zeros(nc)
+        empty = EvalResult(0., 0., 0., 0., 0., maps0, 0., 0., [], 0., [], torch.zeros(1), self.seen)
+        if self._hist is None:
+            return empty
+        out = _ap_device(self._tp, self._conf, self._pcls, self.n, niou, self._hist, nc, self.device)
+        out, hist = out.cpu().numpy(), self._hist.cpu().numpy()       # the one synchronisation
+        if hist[nc]:
+            raise ValueError(f"DetectionEvaluator: {int(hist[nc])} labels have a class outside [0, {nc})")
+        p, r, f1, ntp, ap = _split(out, nc, niou)
+        if not ntp.sum() > 0:                     # test.py:227: no TP at any threshold -> all zero (a TP is always a TP at iouv[0])
+            return empty
+        ap_class = np.flatnonzero(hist[:nc] > 0)
+        p, r, f1, ap = p[ap_class], r[ap_class], f1[ap_class], ap[ap_class]
+        # test.py:229-232
+        ap50, ap75, apm = ap[:, 0], ap[:, 5], ap.mean(1)
+        mp, mr, map50, map75, map_ = p.mean(), r.mean(), ap50.mean(), ap75.mean(), apm.mean()
+        nt = hist[:nc].astype(np.int64)
+        maps = np.zeros(nc) + map_              # test.py:291-293
+        for i, c in enumerate(ap_class):
+            maps[c] = apm[i]
+        return EvalResult(float(mp), float(mr), float(map50), float(map75), float(map_), maps, p, r, ap, f1, ap_class.astype(np.int32),
+                          nt, self.seen)

@@ -1,0 +1,132 @@
+"""Time the GPU mAP evaluator against a test.py-style statistics loop on GPU tensors.
+
+    python tools/eval_bench.py [--batches 16] [--reps 5]
+
+Per 64-image batch (300 detections and 20 labels per image, 3 classes): match_batch + DetectionEvaluator.update
+versus a per-image / per-class Python loop in the style of test.py:132-218 (written here from the rules, on the
+same GPU tensors).  Then DetectionEvaluator.compute() (ap_per_class) for 1013 x 300 detections with 3 classes and
+5000 x 300 with 80 classes.  Prints one JSON line; every time ends in a device synchronisation.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import msod_amd  # noqa: E402,F401
+from msod_amd.utils.metrics import DetectionEvaluator, IOUV  # noqa: E402
+
+
+def make_batch(g, B, nd, nl, nc, H, W, dev):
+    tg, dets, shapes = [], torch.zeros((B, nd, 6)), []
+    for b in range(B):
+        lab = np.column_stack([g.integers(0, nc, nl), g.uniform(0.2, 0.8, (nl, 2)), g.uniform(0.05, 0.3, (nl, 2))])
+        tg += [(b, *l) for l in lab]
+        k = g.integers(0, nl, nd)
+        cxy = lab[k, 1:3] * [W, H] + g.normal(0, 8, (nd, 2))
+        wh = lab[k, 3:5] * [W, H] * np.exp(g.normal(0, 0.25, (nd, 2)))
+        cls = np.where(g.random(nd) < 0.8, lab[k, 0], g.integers(0, nc, nd))
+        dets[b] = torch.from_numpy(np.column_stack([cxy - wh / 2, cxy + wh / 2, np.sort(g.random(nd))[::-1], cls]).astype(np.float32))
+        h0, w0 = 512, 640
+        r = min(H / h0, W / w0)
+        shapes.append(((h0, w0), ((r, r), ((W - w0 * r) / 2, (H - h0 * r) / 2))))
+    return dets.to(dev), torch.full((B,), nd, dtype=torch.int32, device=dev), torch.tensor(tg, dtype=torch.float32, device=dev), shapes
+
+
+def _box_iou(a, b):
+    area = lambda x: (x[:, 2] - x[:, 0]) * (x[:, 3] - x[:, 1])  # noqa: E731
+    inter = (torch.min(a[:, None, 2:], b[:, 2:]) - torch.max(a[:, None, :2], b[:, :2])).clamp(0).prod(2)
+    return inter / (area(a)[:, None] + area(b) - inter)
+
+
+def _native(boxes, img_hw, shape):
+    gain, pad = shape[1][0][0], shape[1][1]
+    boxes[:, [0, 2]] -= pad[0]
+    boxes[:, [1, 3]] -= pad[1]
+    boxes[:, :4] /= gain
+    boxes[:, [0, 2]] = boxes[:, [0, 2]].clamp(0, shape[0][1])
+    boxes[:, [1, 3]] = boxes[:, [1, 3]].clamp(0, shape[0][0])
+    return boxes
+
+
+def loop_stats(dets, counts, targets, img_hw, shapes):
+    """The per-image, per-class statistics loop of test.py, in its style (nonzero, .item() per match), on GPU tensors."""
+    H, W = img_hw
+    iouv = IOUV.to(dets.device)
+    t = targets.clone()
+    t[:, 2:] *= torch.tensor([W, H, W, H], device=dets.device)
+    stats = []
+    for si in range(dets.shape[0]):
+        pred = dets[si, :int(counts[si])]
+        labels = t[t[:, 0] == si, 1:]
+        correct = torch.zeros(pred.shape[0], 10, dtype=torch.bool, device=dets.device)
+        if len(labels):
+            predn = _native(pred[:, :4].clone(), img_hw, shapes[si])
+            xy, wh = labels[:, 1:3], labels[:, 3:5]
+            tbox = _native(torch.cat([xy - wh / 2, xy + wh / 2], 1), img_hw, shapes[si])
+            taken = set()
+            for c in torch.unique(labels[:, 0]):
+                ti = (labels[:, 0] == c).nonzero().view(-1)
+                pi = (pred[:, 5] == c).nonzero().view(-1)
+                if pi.shape[0]:
+                    ious, i = _box_iou(predn[pi], tbox[ti]).max(1)
+                    for j in (ious > iouv[0]).nonzero():
+                        d = ti[i[j]].item()
+                        if d not in taken:
+                            taken.add(d)
+                            correct[pi[j]] = ious[j] > iouv
+        stats.append((correct.cpu(), pred[:, 4].cpu(), pred[:, 5].cpu(), labels[:, 0].tolist()))
+    return stats
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_bench: needs a GPU")
+    dev = torch.device("cuda:0")
+    g = np.random.default_rng(0)
+    H, W = 512, 640
+    batch = make_batch(g, 64, 300, 20, 3, H, W, dev)
+    ev = DetectionEvaluator(3)
+
+    def gpu_step():
+        ev.reset()
+        ev.update(*batch[:3], (H, W), batch[3])
+    res = {"metric": "eval_bench"}
+    res["update_ms_per_64"] = timed(gpu_step, a.reps * 4) * 1e3
+    res["loop_ms_per_64"] = timed(lambda: loop_stats(*batch[:3], (H, W), batch[3]), 2) * 1e3
+    for name, n_img, nc in (("flir_1013x300_nc3", 1013, 3), ("coco_5000x300_nc80", 5000, 80)):
+        ev = DetectionEvaluator(nc)
+        b64 = make_batch(g, 64, 300, 20, nc, H, W, dev)
+        left = n_img
+        while left > 0:
+            k = min(64, left)
+            ev.update(b64[0][:k].contiguous(), b64[1][:k].contiguous(), b64[2][b64[2][:, 0] < k], (H, W), b64[3][:k])
+            left -= k
+        torch.cuda.synchronize()
+        res[f"compute_ms_{name}"] = timed(ev.compute, a.reps) * 1e3
+        res[f"map_{name}"] = ev.compute().map
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
