@@ -366,6 +366,33 @@ long cft_eval_ap_workspace_bytes(long n, int nc);
 int cft_eval_ap(const unsigned short* tp_bits, const float* conf, const int* pcls, long n, int niou, const int* label_hist, int nc,
                 const double* px, const double* x, void* workspace, long workspace_bytes, double* out, void* stream);
 
+/*
+ * ComputeLoss of the reference (utils/loss.py:88-216) and its gradient with respect to the head outputs.
+ *   p[l]      : host array of nl (1..5) device pointers, float32 contiguous [B, na, ny[l], nx[l], nc + 5] (Detect's raw list)
+ *   ny, nx    : host arrays [nl]
+ *   targets   : device float32 [nt, 6] = image, class, x, y, w, h (normalised); may be NULL when nt = 0
+ *   anchors   : device float32 [nl, na, 2] in grid units (Detect.anchors)
+ *   hyp       : HOST float64 [10] = box, obj, cls, cls_pw, obj_pw, anchor_t, fl_gamma, cp, cn, gr (cp / cn = smooth_BCE)
+ *   balance   : device float64 [nl], read; with autobalance also updated as the reference does (ssi = stride-16 level)
+ * cft_loss_forward writes loss [1] = (lbox + lobj + lcls) * B and items [4] = (lbox, lobj, lcls, loss) (device float32), and ORs
+ * into err (device int): 1 = a target whose image index is outside [0, B) passed the anchor test, 2 = nc > 1 and a target whose
+ * class is outside [0, nc) passed it.  Such targets are skipped (the reference raises on them).
+ * build_targets' candidates are the reference's, in its order, compacted with prefix scans (capacity 5 * na * nt per level).
+ * cft_loss_backward writes every element of grad[l] (host array of device pointers, shaped as p[l]) = d(loss * g) / dp[l],
+ * g = grad_loss[0] (device); it reads what the last cft_loss_forward on the same workspace left there.
+ * workspace: >= cft_loss_workspace_bytes(...) bytes, 256-byte aligned.  No allocation, no synchronisation, no float atomics.
+ */
+long cft_loss_workspace_bytes(int nl, int B, int na, const int* ny, const int* nx, int nc, int nt);
+int cft_loss_forward(int nl, const float* const* p, int B, int na, const int* ny, const int* nx, int nc, const float* targets, int nt,
+                     const float* anchors, const double* hyp, double* balance, int autobalance, int ssi, void* workspace,
+                     long workspace_bytes, float* loss, float* items, int* err, void* stream);
+/* byte offsets of the candidate lists in a forward's workspace: out[0] cell (int [nl][cap], ((b * na + a) * ny + gj) * nx + gi),
+ * out[1] class (int [nl][cap]), out[2] tbox (float4 [nl][cap]), out[3] candidate counts (int [nl]); returns cap = 5 * na * nt */
+long cft_loss_workspace_offsets(int nl, int B, int na, const int* ny, const int* nx, int nc, int nt, long* out);
+int cft_loss_backward(int nl, const float* const* p, int B, int na, const int* ny, const int* nx, int nc, int nt, const float* anchors,
+                      const double* hyp, const float* grad_loss, float* const* grad, void* workspace, long workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

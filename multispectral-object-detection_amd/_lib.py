@@ -15,12 +15,12 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: experiments with an alternative build, e.g. the probe library)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip")
+SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "loss.hip")
 
 HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "conv_gemm_asm.inc")
 
 CFT_BF16, CFT_F32, CFT_F16 = 0, 1, 2
-ABI_VERSION = 13
+ABI_VERSION = 14
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 
 _c = ctypes
@@ -66,6 +66,10 @@ SIGNATURES = {
     "cft_eval_match": [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "cft_eval_ap_workspace_bytes": [_l, _i],         # returns long (bytes)
     "cft_eval_ap": [_vp, _vp, _vp, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp],
+    "cft_loss_workspace_bytes": [_i, _i, _i, _vp, _vp, _i, _i],      # returns long (bytes)
+    "cft_loss_forward": [_i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp],
+    "cft_loss_workspace_offsets": [_i, _i, _i, _vp, _vp, _i, _i, _vp],   # returns long (capacity)
+    "cft_loss_backward": [_i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp],
 }
 
 _lib = None
@@ -124,6 +128,8 @@ def load():
     lib.cft_batchnorm_train_workspace.restype = ctypes.c_long
     lib.cft_eval_match_workspace_bytes.restype = ctypes.c_long
     lib.cft_eval_ap_workspace_bytes.restype = ctypes.c_long
+    lib.cft_loss_workspace_bytes.restype = ctypes.c_long
+    lib.cft_loss_workspace_offsets.restype = ctypes.c_long
     _lib = lib
     return lib
 
