@@ -26,6 +26,10 @@
 extern "C" {
 #endif
 
+/* Bump with every change of a prototype below (history: csrc/runtime.hip).  The Python binding reads this line, the enums and
+ * every prototype from this file: it is the only description of the ABI. */
+#define CFT_ABI_VERSION 14
+
 enum { CFT_BF16 = 0, CFT_F32 = 1, CFT_F16 = 2 };
 enum { CFT_ACT_NONE = 0, CFT_ACT_SILU = 1, CFT_ACT_GELU = 2 };
 enum {

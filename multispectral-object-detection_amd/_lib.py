@@ -5,6 +5,7 @@ op raises.  ``build()`` compiles the library in-tree with hipcc (cross-compiles 
 """
 import ctypes
 import os
+import re
 import subprocess
 
 # torch must be imported BEFORE the library is dlopen'ed: torch ships its own libamdhip64 and a
@@ -17,60 +18,46 @@ LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "loss.hip")
 
+HEADER = os.path.join(_HERE, "..", "include", "cft_hip.h")
 HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "conv_gemm_asm.inc")
 
-CFT_BF16, CFT_F32, CFT_F16 = 0, 1, 2
-ABI_VERSION = 14
-ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong}
+_RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+_TYPE_WORDS = frozenset("void char short int long float double signed unsigned const".split())
 
-_c = ctypes
-_vp, _i, _l, _f = _c.c_void_p, _c.c_int, _c.c_long, _c.c_float
 
-# name -> argtypes; every function returns int except cft_last_error.  Mirrors include/cft_hip.h.
-SIGNATURES = {
-    "cft_abi_version": [],
-    "cft_device_check": [],
-    "cft_clock_probe": [_vp, _i, _c.POINTER(_c.c_int), _vp],
-    "cft_conv2d_chain": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_conv2d_chain_ok": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i],
-    "cft_conv2d_chain_res": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_linear_splitk": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_layernorm_reduce": [_vp, _vp, _i, _vp, _vp, _vp, _l, _i, _f, _i, _vp],
-    "cft_conv2d": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_set_conv_variant": [_i],
-    "cft_bottleneck": [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_bottleneck_pack_w2": [_vp, _i, _i, _vp, _i, _vp],
-    "cft_focus_s2d": [_vp, _vp, _i, _i, _i, _i, _vp],
-    "cft_focus_s2d_u8": [_vp, _l, _l, _l, _vp, _i, _i, _i, _f, _i, _vp],
-    "cft_focus_conv": [_vp, _i, _l, _l, _l, _f, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_letterbox_u8": [_vp, _i, _i, _l, _vp, _i, _i, _l, _l, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_to_nhwc": [_vp, _i, _l, _l, _l, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_spp_maxpool": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_copy_channels": [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_add": [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _l, _i, _i, _vp],
-    "cft_gpt_tokenize": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "cft_layernorm": [_vp, _vp, _vp, _vp, _l, _i, _f, _i, _vp],
-    "cft_attention": [_vp, _vp, _i, _i, _i, _i, _i, _f, _c.c_ulonglong, _vp],
-    "cft_batchnorm_train": [_vp, _i, _i, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _l, _vp],
-    "cft_dropout": [_vp, _l, _f, _c.c_ulonglong, _i, _vp],
-    "cft_batchnorm_train_workspace": [_l, _i],      # returns long (bytes)
-    "cft_gpt_upsample_add": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_gpt_upsample_add2": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_gpt_tokenize_grid": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_attention_tokens": [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _c.c_ulonglong, _vp],
-    "cft_gpt_upsample_add_grid": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_gpt_upsample_add2_grid": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "cft_nms": [_vp, _i, _i, _i, _f, _f, _i, _i, _vp, _i, _i, _vp, _l, _vp, _vp, _vp],
-    "cft_detect_decode": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _l, _l, _vp],
-    "cft_eval_match_workspace_bytes": [_i, _i],      # returns long (bytes)
-    "cft_eval_match": [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
-    "cft_eval_ap_workspace_bytes": [_l, _i],         # returns long (bytes)
-    "cft_eval_ap": [_vp, _vp, _vp, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp],
-    "cft_loss_workspace_bytes": [_i, _i, _i, _vp, _vp, _i, _i],      # returns long (bytes)
-    "cft_loss_forward": [_i, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp, _vp],
-    "cft_loss_workspace_offsets": [_i, _i, _i, _vp, _vp, _i, _i, _vp],   # returns long (capacity)
-    "cft_loss_backward": [_i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp],
-}
+def parse_header(text):
+    """``(signatures, constants)`` of a header in the dialect of include/cft_hip.h: ``ret cft_name(args);`` prototypes whose arguments
+    are pointers (-> c_void_p, device and host alike: callers pass ``data_ptr()`` integers, arrays or ``byref``) or named int / long /
+    float / unsigned long long scalars -> name: (restype, argtypes); ``CFT_X = n`` enumerators and ``#define CFT_X n`` -> name: n.
+    Anything else in a prototype raises with the prototype's name: a type is never guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {k: int(v) for k, v in re.findall(r"(?:#define\s+|\b)(CFT_\w+)\s*=?\s*(-?\d+)\b", text)}
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(cft_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise ValueError(f"{name}: unknown return type '{ret}'")
+        argtypes = []
+        for arg in ([] if args.strip() in ("", "void") else args.split(",")):
+            *kind, pname = [w for w in arg.split() if w != "const"] or [""]
+            if "*" in arg:
+                argtypes.append(ctypes.c_void_p)
+            elif " ".join(kind) in _SCALARS and pname not in _TYPE_WORDS:
+                argtypes.append(_SCALARS[" ".join(kind)])
+            else:
+                raise ValueError(f"{name}: unknown parameter type in '{' '.join(arg.split())}' (scalars are named int / long / float / unsigned long long)")
+        sigs[name] = (_RETURNS[ret], argtypes)
+    return sigs, consts
+
+
+# name -> (restype, argtypes) of every entry point, and the header's constants: include/cft_hip.h is the only description of the ABI
+with open(HEADER) as _fh:
+    SIGNATURES, _consts = parse_header(_fh.read())
+ABI_VERSION = _consts["CFT_ABI_VERSION"]
+CFT_BF16, CFT_F32, CFT_F16 = (_consts[k] for k in ("CFT_BF16", "CFT_F32", "CFT_F16"))
+ACT_NONE, ACT_SILU, ACT_GELU = (_consts[k] for k in ("CFT_ACT_NONE", "CFT_ACT_SILU", "CFT_ACT_GELU"))
 
 _lib = None
 
@@ -78,7 +65,7 @@ _lib = None
 def build(verbose=False):
     """Compile every HIP source for gfx950 into ``libcft_hip.so`` next to this file."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(_HERE, "..", "include", "cft_hip.h")]
+    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER]
     newest = max(os.path.getmtime(p) for p in srcs + hdrs)
     if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
         return LIB_PATH
@@ -119,17 +106,9 @@ def load():
             f"{LIB_PATH} not found: the HIP kernels are the only execution path of this package. "
             "Build them with `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = ABI mismatch, let it propagate
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
-    lib.cft_last_error.argtypes = []
-    lib.cft_last_error.restype = ctypes.c_char_p
-    lib.cft_batchnorm_train_workspace.restype = ctypes.c_long
-    lib.cft_eval_match_workspace_bytes.restype = ctypes.c_long
-    lib.cft_eval_ap_workspace_bytes.restype = ctypes.c_long
-    lib.cft_loss_workspace_bytes.restype = ctypes.c_long
-    lib.cft_loss_workspace_offsets.restype = ctypes.c_long
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -95,8 +95,7 @@ class PendingConv(_Pending):
     @property
     def shape(self):
         B, _, H, W = self.x.shape
-        k, s = self.conv.conv.kernel_size[0], self.conv.conv.stride[0]
-        return torch.Size((B, self.conv.conv.out_channels, (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1))
+        return torch.Size((B, self.conv.conv.out_channels, *ops.conv_out_size(H, W, self.conv.conv.kernel_size[0], self.conv.conv.stride[0])))
 
 
 def resolve(x):

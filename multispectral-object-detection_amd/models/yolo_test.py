@@ -534,8 +534,7 @@ class Model(nn.Module):
             if isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 4:
                 B, _, H, W = shape or t.shape
                 if type(m) is Conv:
-                    k, s_ = m.conv.kernel_size[0], m.conv.stride[0]
-                    H, W = (H + 2 * (k // 2) - k) // s_ + 1, (W + 2 * (k // 2) - k) // s_ + 1
+                    H, W = ops.conv_out_size(H, W, m.conv.kernel_size[0], m.conv.stride[0])
                 buf = cbufs.get(cidx)
                 if buf is None:
                     buf = cbufs[cidx] = ops.new_nhwc(B, H, W, total, t.dtype, t.device)

@@ -140,7 +140,8 @@ def pack_conv(weight, bias, dtype, k=None, s=1, cin_pad=None, device=None, n_tru
 # ------------------------------------------------------------------------------ launch timing
 # When a list is installed here every GEMM launch is bracketed by HIP events recorded on the launch
 # stream (bench.py uses it to time the dominant kernel family live): entries are
-# (tile_family, algorithmic_flops, start_event, end_event).
+# (tile_family, algorithmic_flops, start_event, end_event, algorithmic_bytes).  The callers build the label and the byte count whether
+# or not a log is installed (a few integer products and one f-string per launch; graph replay never comes here).
 _launch_log = None
 
 
@@ -161,15 +162,14 @@ def _timed(name, flops, abytes, fn):
     return st
 
 
-def _timed_gemm(lib, rows, pk, args, abytes=0.0, kind="conv"):
-    if _launch_log is None:
-        return lib.cft_conv2d(*args)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    st = lib.cft_conv2d(*args)
-    e1.record()
-    _launch_log.append((f"{kind}_k{pk.k}s{pk.s}_n{pk.n}_K{pk.kpad}", rows * pk.flops_per_row, e0, e1, abytes))
-    return st
+def conv_out_size(H, W, k, s):
+    """(Ho, Wo) of a k x k convolution with stride s and padding k // 2 on an H x W input."""
+    p = k // 2
+    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+
+
+def _bias_ptr(pk):
+    return None if pk.bias is None else pk.bias.data_ptr()
 
 
 # ------------------------------------------------------------------------------ ops
@@ -180,8 +180,7 @@ def conv2d(x, pk, act, residual=None, out=None, out_dtype=None):
     B, C, H, W = x.shape
     if C != pk.cin:
         raise ValueError(f"conv2d: input has {C} channels, packed weight expects {pk.cin}")
-    p = pk.k // 2
-    Ho, Wo = (H + 2 * p - pk.k) // pk.s + 1, (W + 2 * p - pk.k) // pk.s + 1
+    Ho, Wo = conv_out_size(H, W, pk.k, pk.s)
     if out is None:
         out = new_nhwc(B, Ho, Wo, pk.n, out_dtype or x.dtype, x.device)
     if tuple(out.shape) != (B, pk.n, Ho, Wo):
@@ -197,10 +196,9 @@ def conv2d(x, pk, act, residual=None, out=None, out_dtype=None):
     es_in, es_out = x.element_size(), out.element_size()
     abytes = (B * H * W * pk.cin * es_in + B * Ho * Wo * pk.n_valid * es_out + pk.w.numel() * es_in
               + (0 if residual is None else residual.numel() * residual.element_size()))
-    st = _timed_gemm(lib, B * Ho * Wo, pk,
-                     (x.data_ptr(), pk.w.data_ptr(), pk.bias.data_ptr() if pk.bias is not None else None, rp,
-                      out.data_ptr(), B, H, W, pk.cin, ldx, 0, pk.n, pk.kpad, pk.k, pk.s,
-                      ldy, 0, ldr, 0, act, _dt(x.dtype), _dt(out.dtype), rdt, _stream()), abytes)
+    st = _timed(f"conv_k{pk.k}s{pk.s}_n{pk.n}_K{pk.kpad}", B * Ho * Wo * pk.flops_per_row, abytes,
+                lambda: lib.cft_conv2d(x.data_ptr(), pk.w.data_ptr(), _bias_ptr(pk), rp, out.data_ptr(), B, H, W, pk.cin, ldx, 0,
+                                       pk.n, pk.kpad, pk.k, pk.s, ldy, 0, ldr, 0, act, _dt(x.dtype), _dt(out.dtype), rdt, _stream()))
     _lib.check(st, "cft_conv2d")
     return out
 
@@ -216,12 +214,18 @@ def conv2d_chain_ok_geometry(B, H, W, dtype, pk1, pk2, ldx=None, ldy=None):
     return bool(_lib.load().cft_conv2d_chain_ok(B, H, W, pk1.cin, ldx or pk1.cin, pk1.n, pk1.kpad, pk1.k, pk1.s, pk2.n, ldy or pk2.n, _dt(dtype)))
 
 
+def _chain_geometry(x, pk1):
+    """(B, H, W, dtype, ldx) of ``x`` for the ``_geometry`` predicates, or None when ``x`` is not a 4-D GPU tensor of ``pk1.cin`` channels."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.shape[1] == pk1.cin):
+        return None
+    ldx = x.stride(3) if (x.stride(1) == 1 and x.stride(3) >= x.shape[1]) else None      # (another layout is converted to dense NHWC first)
+    return x.shape[0], x.shape[2], x.shape[3], x.dtype, ldx
+
+
 def conv2d_chain_ok(x, pk1, pk2):
     """True when ``conv2d_chain`` takes this pair: conv ``pk1`` (SiLU) then the pointwise conv ``pk2`` on its output (cft_conv2d_chain_ok)."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.shape[1] == pk1.cin):
-        return False
-    ldx = x.stride(3) if (x.stride(1) == 1 and x.stride(3) >= x.shape[1]) else None      # (another layout is converted to dense NHWC first)
-    return conv2d_chain_ok_geometry(x.shape[0], x.shape[2], x.shape[3], x.dtype, pk1, pk2, ldx=ldx)
+    g = _chain_geometry(x, pk1)
+    return g is not None and conv2d_chain_ok_geometry(*g[:4], pk1, pk2, ldx=g[4])
 
 
 def conv2d_chain(x, pk1, pk2, act2, out=None):
@@ -232,8 +236,7 @@ def conv2d_chain(x, pk1, pk2, act2, out=None):
         raise ValueError("conv2d_chain: layer pair not eligible (conv2d_chain_ok)")
     x, ldx = as_nhwc(x)
     B, C, H, W = x.shape
-    p = pk1.k // 2
-    Ho, Wo = (H + 2 * p - pk1.k) // pk1.s + 1, (W + 2 * p - pk1.k) // pk1.s + 1
+    Ho, Wo = conv_out_size(H, W, pk1.k, pk1.s)
     if out is None:
         out = new_nhwc(B, Ho, Wo, pk2.n, x.dtype, x.device)
     if tuple(out.shape) != (B, pk2.n, Ho, Wo) or out.dtype != x.dtype:
@@ -243,8 +246,7 @@ def conv2d_chain(x, pk1, pk2, act2, out=None):
     es = x.element_size()
     M = B * Ho * Wo
     abytes = B * H * W * pk1.cin * es + M * pk2.n_valid * es + (pk1.w.numel() + pk2.w.numel()) * es
-    args = (x.data_ptr(), pk1.w.data_ptr(), pk1.bias.data_ptr() if pk1.bias is not None else None,
-            pk2.w.data_ptr(), pk2.bias.data_ptr() if pk2.bias is not None else None, out.data_ptr(),
+    args = (x.data_ptr(), pk1.w.data_ptr(), _bias_ptr(pk1), pk2.w.data_ptr(), _bias_ptr(pk2), out.data_ptr(),
             B, H, W, pk1.cin, ldx, 0, pk1.n, pk1.kpad, pk1.k, pk1.s, pk2.n, ldy, 0, act2, _dt(x.dtype), _stream())
     # counted with the GEMM family: both layers' FLOPs, one launch
     st = _timed(f"conv_chain_k{pk1.k}s{pk1.s}_n{pk1.n}_K{pk1.kpad}+{pk2.kpad}", M * (pk1.flops_per_row + pk2.flops_per_row), abytes,
@@ -256,26 +258,23 @@ def conv2d_chain(x, pk1, pk2, act2, out=None):
 CHAIN_RES_MIN_ROWS = 192 * 256      # output pixels from which the chained kernel's 256-row tiles fill >= 3/4 of the 256 CUs
 
 
+def conv2d_chain_res_ok_geometry(B, H, W, dtype, pk1, pk2, any_size=False, ldx=None):
+    """True when ``conv2d_chain_res`` takes the pair on a [B, pk1.cin, H, W] input of ``dtype``: ``conv2d_chain_ok_geometry``, a 256-channel
+    first layer (the four-image form of the kernel) and - unless ``any_size`` - enough output pixels: the chained kernel exists in the
+    256 x 256 tile only, and below ~49 000 pixels (cfg3: < 32 pairs at 640 x 640) the separate launches run on smaller tiles with 4 - 8 x
+    the workgroups (measured at 8 pairs: 71 against ~33 us per pair of launches, profiles/r05_splitk_ab.md).  ``ldx`` as in
+    ``conv2d_chain_ok_geometry``; by default input and outputs are DENSE (what ``C3.forward`` passes: the hidden tensor and y1 are dense;
+    the shortcut's own row stride is checked at launch)."""
+    if not (pk1.n == 256 and conv2d_chain_ok_geometry(B, H, W, dtype, pk1, pk2, ldx=ldx)):
+        return False
+    Ho, Wo = conv_out_size(H, W, pk1.k, pk1.s)
+    return any_size or B * Ho * Wo >= CHAIN_RES_MIN_ROWS
+
+
 def conv2d_chain_res_ok(x, pk1, pk2, any_size=False):
-    """True when ``conv2d_chain_res`` takes the pair: ``conv2d_chain_ok``, a 256-channel first layer (the four-image form of the kernel) and -
-    unless ``any_size`` - enough output pixels: the chained kernel exists in the 256 x 256 tile only, and below ~49 000 pixels (cfg3: < 32 pairs
-    at 640 x 640) the separate launches run on smaller tiles with 4 - 8 x the workgroups (measured at 8 pairs: 71 against ~33 us per pair of
-    launches, profiles/r05_splitk_ab.md)."""
-    if not (pk1.n == 256 and conv2d_chain_ok(x, pk1, pk2)):
-        return False
-    p_ = pk1.k // 2
-    rows = x.shape[0] * ((x.shape[2] + 2 * p_ - pk1.k) // pk1.s + 1) * ((x.shape[3] + 2 * p_ - pk1.k) // pk1.s + 1)
-    return any_size or rows >= CHAIN_RES_MIN_ROWS
-
-
-def conv2d_chain_res_ok_geometry(B, H, W, dtype, pk1, pk2, any_size=False):
-    """``conv2d_chain_res_ok`` for DENSE input / output tensors of the given pixel grid (what ``C3.forward`` passes: the hidden tensor and y1 are
-    dense; the shortcut's own row stride is checked at launch)."""
-    if not (pk1.n == 256 and conv2d_chain_ok_geometry(B, H, W, dtype, pk1, pk2)):
-        return False
-    p_ = pk1.k // 2
-    rows = B * ((H + 2 * p_ - pk1.k) // pk1.s + 1) * ((W + 2 * p_ - pk1.k) // pk1.s + 1)
-    return any_size or rows >= CHAIN_RES_MIN_ROWS
+    """``conv2d_chain_res_ok_geometry`` of the GPU tensor ``x`` (False for anything else)."""
+    g = _chain_geometry(x, pk1)
+    return g is not None and conv2d_chain_res_ok_geometry(*g[:4], pk1, pk2, any_size=any_size, ldx=g[4])
 
 
 def conv2d_chain_res(x, pk1, res, pk2, act2, out1=None, out2=None):
@@ -287,8 +286,7 @@ def conv2d_chain_res(x, pk1, res, pk2, act2, out1=None, out2=None):
         raise ValueError("conv2d_chain_res: layer pair not eligible (conv2d_chain_res_ok)")
     x, ldx = as_nhwc(x)
     B, C, H, W = x.shape
-    p = pk1.k // 2
-    Ho, Wo = (H + 2 * p - pk1.k) // pk1.s + 1, (W + 2 * p - pk1.k) // pk1.s + 1
+    Ho, Wo = conv_out_size(H, W, pk1.k, pk1.s)
     if tuple(res.shape) != (B, pk1.n, Ho, Wo) or res.dtype != x.dtype:
         raise ValueError(f"conv2d_chain_res: residual has shape {tuple(res.shape)}, expected {(B, pk1.n, Ho, Wo)}")
     ldr = _view_ld(res, "conv2d_chain_res residual")
@@ -303,8 +301,7 @@ def conv2d_chain_res(x, pk1, res, pk2, act2, out1=None, out2=None):
     es = x.element_size()
     M = B * Ho * Wo
     abytes = (B * H * W * pk1.cin + 2 * M * pk1.n_valid + M * pk2.n_valid + pk1.w.numel() + pk2.w.numel()) * es
-    args = (x.data_ptr(), pk1.w.data_ptr(), pk1.bias.data_ptr() if pk1.bias is not None else None, res.data_ptr(), out1.data_ptr(),
-            pk2.w.data_ptr(), pk2.bias.data_ptr() if pk2.bias is not None else None, out2.data_ptr(),
+    args = (x.data_ptr(), pk1.w.data_ptr(), _bias_ptr(pk1), res.data_ptr(), out1.data_ptr(), pk2.w.data_ptr(), _bias_ptr(pk2), out2.data_ptr(),
             B, H, W, pk1.cin, ldx, 0, pk1.n, pk1.kpad, pk1.k, pk1.s, ldr, 0, ldy1, 0, pk2.n, ldy2, 0, act2, _dt(x.dtype), _stream())
     st = _timed(f"conv_chainres_k{pk1.k}s{pk1.s}_n{pk1.n}_K{pk1.kpad}+{pk2.kpad}", M * (pk1.flops_per_row + pk2.flops_per_row), abytes,
                 lambda: lib.cft_conv2d_chain_res(*args))
@@ -345,20 +342,14 @@ def bottleneck(x, pk1, pk2, shortcut, out=None):
         pk2.w_stages = torch.empty_like(pk2.w)
         _lib.check(lib.cft_bottleneck_pack_w2(pk2.w.data_ptr(), pk2.kpad, C, pk2.w_stages.data_ptr(), _dt(x.dtype), _stream()),
                    "cft_bottleneck_pack_w2")
-    args = (x.data_ptr(), ldx, 0, pk1.w.data_ptr(), pk1.kpad, pk1.bias.data_ptr() if pk1.bias is not None else None,
-            pk2.w.data_ptr(), pk2.kpad, pk2.w_stages.data_ptr() if pk2.w_stages is not None else None,
-            pk2.bias.data_ptr() if pk2.bias is not None else None,
+    args = (x.data_ptr(), ldx, 0, pk1.w.data_ptr(), pk1.kpad, _bias_ptr(pk1),
+            pk2.w.data_ptr(), pk2.kpad, None if pk2.w_stages is None else pk2.w_stages.data_ptr(), _bias_ptr(pk2),
             out.data_ptr(), ldy, 0, B, H, W, C, 1 if shortcut else 0, _dt(x.dtype), _stream())
-    if _launch_log is None:
-        st = lib.cft_bottleneck(*args)
-    else:   # counted with the GEMM family: both convolutions' FLOPs, one launch
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        st = lib.cft_bottleneck(*args)
-        e1.record()
-        rows = B * H * W
-        abytes = rows * C * 2 * (3 if shortcut else 2) + (pk1.w.numel() + pk2.w.numel()) * 2
-        _launch_log.append((f"conv_bneck_c{C}_K{pk1.kpad}+{pk2.kpad}", rows * (pk1.flops_per_row + pk2.flops_per_row), e0, e1, abytes))
+    rows = B * H * W
+    abytes = rows * C * 2 * (3 if shortcut else 2) + (pk1.w.numel() + pk2.w.numel()) * 2
+    # counted with the GEMM family: both convolutions' FLOPs, one launch
+    st = _timed(f"conv_bneck_c{C}_K{pk1.kpad}+{pk2.kpad}", rows * (pk1.flops_per_row + pk2.flops_per_row), abytes,
+                lambda: lib.cft_bottleneck(*args))
     _lib.check(st, "cft_bottleneck")
     return out
 
@@ -377,10 +368,9 @@ def linear(x, pk, act=ACT_NONE, residual=None, out=None, out_dtype=None):
     lib = _lib.load()
     abytes = (rows * K * x.element_size() + rows * pk.n_valid * out.element_size() + pk.w.numel() * x.element_size()
               + (0 if residual is None else rows * pk.n_valid * residual.element_size()))
-    st = _timed_gemm(lib, rows, pk,
-                     (x.data_ptr(), pk.w.data_ptr(), pk.bias.data_ptr() if pk.bias is not None else None, rp,
-                      out.data_ptr(), 1, 1, rows, pk.cin, x.stride(0), 0, pk.n, pk.kpad, 1, 1,
-                      out.stride(0), 0, ldr, 0, act, _dt(x.dtype), _dt(out.dtype), rdt, _stream()), abytes, kind="linear")
+    st = _timed(f"linear_k{pk.k}s{pk.s}_n{pk.n}_K{pk.kpad}", rows * pk.flops_per_row, abytes,
+                lambda: lib.cft_conv2d(x.data_ptr(), pk.w.data_ptr(), _bias_ptr(pk), rp, out.data_ptr(), 1, 1, rows, pk.cin, x.stride(0), 0,
+                                       pk.n, pk.kpad, 1, 1, out.stride(0), 0, ldr, 0, act, _dt(x.dtype), _dt(out.dtype), rdt, _stream()))
     _lib.check(st, "cft_conv2d(linear)")
     return out
 
@@ -425,7 +415,7 @@ def linear_splitk(x, pk, splits):
     lib = _lib.load()
     abytes = rows * K * x.element_size() + splits * rows * pk.n_valid * 4 + pk.w.numel() * x.element_size()
     st = _timed(f"linear_k{pk.k}s{pk.s}_n{pk.n}_K{pk.kpad}", rows * pk.flops_per_row, abytes,
-                lambda: lib.cft_linear_splitk(x.data_ptr(), pk.w.data_ptr(), pk.bias.data_ptr() if pk.bias is not None else None, parts.data_ptr(),
+                lambda: lib.cft_linear_splitk(x.data_ptr(), pk.w.data_ptr(), _bias_ptr(pk), parts.data_ptr(),
                                               rows, pk.cin, x.stride(0), pk.n, pk.kpad, splits, _dt(x.dtype), _stream()))
     _lib.check(st, "cft_linear_splitk")
     return parts
@@ -512,18 +502,12 @@ def focus_conv(img, pk, act, dtype):
     out = new_nhwc(B, H // 2, W // 2, pk.n, dtype, img.device)
     lib = _lib.load()
     args = (img.data_ptr(), kind, img.stride(0), img.stride(1), img.stride(2), 1.0 / 255.0 if u8 else 1.0,
-            pk.w.data_ptr(), pk.kpad, pk.bias.data_ptr() if pk.bias is not None else None, out.data_ptr(),
+            pk.w.data_ptr(), pk.kpad, _bias_ptr(pk), out.data_ptr(),
             _view_ld(out, "focus_conv out"), 0, B, H, W, pk.n, act, _dt(dtype), _stream())
-    if _launch_log is None:
-        st = lib.cft_focus_conv(*args)
-    else:   # counted with the GEMM family (it is the same implicit-GEMM MFMA work, on a dedicated kernel)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        st = lib.cft_focus_conv(*args)
-        e1.record()
-        rows = B * (H // 2) * (W // 2)
-        abytes = img.numel() * es + rows * pk.n_valid * 2 + pk.w.numel() * 2
-        _launch_log.append((f"conv_focus_k3s1_n{pk.n}_K{pk.kpad}", rows * pk.flops_per_row, e0, e1, abytes))
+    rows = B * (H // 2) * (W // 2)
+    abytes = img.numel() * es + rows * pk.n_valid * 2 + pk.w.numel() * 2
+    # counted with the GEMM family (it is the same implicit-GEMM MFMA work, on a dedicated kernel)
+    st = _timed(f"conv_focus_k3s1_n{pk.n}_K{pk.kpad}", rows * pk.flops_per_row, abytes, lambda: lib.cft_focus_conv(*args))
     _lib.check(st, "cft_focus_conv")
     return out
 
@@ -584,6 +568,14 @@ def _grid(grid):
     return va, ha
 
 
+def _grid_entry(lib, name, va, ha):
+    """(function, label, extra arguments) of a GPT token kernel on a va x ha anchor grid: the specialised 8 x 8 kernel ``name``, or
+    ``name_grid`` with its (va, ha) arguments on any other grid."""
+    if (va, ha) == (8, 8):
+        return getattr(lib, name), name, ()
+    return getattr(lib, name + "_grid"), name + "_grid", (va, ha)
+
+
 def gpt_tokenize(rgb, ir, pos_emb, grid=ANCHOR_GRID):
     """-> float32 tokens [B, 2*va*ha, C] (adaptive average pool of both streams to the ``grid`` = (va, ha) anchors, + pos_emb)."""
     _require_cuda(rgb, "gpt_tokenize")
@@ -594,14 +586,11 @@ def gpt_tokenize(rgb, ir, pos_emb, grid=ANCHOR_GRID):
     T = 2 * va * ha
     tokens = torch.empty((B, T, C), dtype=torch.float32, device=rgb.device)
     lib = _lib.load()
-    if (va, ha) == (8, 8):
-        fn = lambda: lib.cft_gpt_tokenize(rgb.data_ptr(), ld_r, 0, ir.data_ptr(), ld_i, 0, pos_emb.data_ptr(), tokens.data_ptr(),  # noqa: E731
-                                          B, H, W, C, _dt(rgb.dtype), _stream())
-    else:
-        fn = lambda: lib.cft_gpt_tokenize_grid(rgb.data_ptr(), ld_r, 0, ir.data_ptr(), ld_i, 0, pos_emb.data_ptr(), tokens.data_ptr(),  # noqa: E731
-                                               B, H, W, C, va, ha, _dt(rgb.dtype), _stream())
-    st = _timed("cft_tokenize", 0.0, 2.0 * B * H * W * C * rgb.element_size() + B * T * C * 4, fn)
-    _lib.check(st, "cft_gpt_tokenize" if (va, ha) == (8, 8) else "cft_gpt_tokenize_grid")
+    fn, label, grid_args = _grid_entry(lib, "cft_gpt_tokenize", va, ha)
+    st = _timed("cft_tokenize", 0.0, 2.0 * B * H * W * C * rgb.element_size() + B * T * C * 4,
+                lambda: fn(rgb.data_ptr(), ld_r, 0, ir.data_ptr(), ld_i, 0, pos_emb.data_ptr(), tokens.data_ptr(),
+                           B, H, W, C, *grid_args, _dt(rgb.dtype), _stream()))
+    _lib.check(st, label)
     return tokens
 
 
@@ -656,13 +645,10 @@ def gpt_upsample_add(tokens, s, base, H, W, dtype, grid=None):
             raise ValueError("gpt_upsample_add: base shape/dtype mismatch")
         bp = base.data_ptr()
     lib = _lib.load()
-    if (va, ha) == (8, 8):
-        fn = lambda: lib.cft_gpt_upsample_add(tokens.data_ptr(), s, bp, ldb, 0, out.data_ptr(), C, 0, B, H, W, C, _dt(dtype), _stream())  # noqa: E731
-    else:
-        fn = lambda: lib.cft_gpt_upsample_add_grid(tokens.data_ptr(), s, bp, ldb, 0, out.data_ptr(), C, 0, B, H, W, C, va, ha,  # noqa: E731
-                                                   _dt(dtype), _stream())
-    st = _timed("cft_upsample_add", 0.0, (2.0 if bp else 1.0) * B * H * W * C * out.element_size(), fn)
-    _lib.check(st, "cft_gpt_upsample_add" if (va, ha) == (8, 8) else "cft_gpt_upsample_add_grid")
+    fn, label, grid_args = _grid_entry(lib, "cft_gpt_upsample_add", va, ha)
+    st = _timed("cft_upsample_add", 0.0, (2.0 if bp else 1.0) * B * H * W * C * out.element_size(),
+                lambda: fn(tokens.data_ptr(), s, bp, ldb, 0, out.data_ptr(), C, 0, B, H, W, C, *grid_args, _dt(dtype), _stream()))
+    _lib.check(st, label)
     return out
 
 
@@ -703,15 +689,11 @@ def gpt_upsample_add_dual(tokens, base0, base1, H, W, dtype, sum_out=None, want_
     else:
         sum_out = None
     lib = _lib.load()
-    if (va, ha) == (8, 8):
-        fn = lambda: lib.cft_gpt_upsample_add2(tokens.data_ptr(), base0.data_ptr(), ldb0, 0, base1.data_ptr(), ldb1, 0,  # noqa: E731
-                                               out0.data_ptr(), C, 0, out1.data_ptr(), C, 0, sp, lds, 0, B, H, W, C, _dt(dtype), _stream())
-    else:
-        fn = lambda: lib.cft_gpt_upsample_add2_grid(tokens.data_ptr(), base0.data_ptr(), ldb0, 0, base1.data_ptr(), ldb1, 0,  # noqa: E731
-                                                    out0.data_ptr(), C, 0, out1.data_ptr(), C, 0, sp, lds, 0, B, H, W, C, va, ha, _dt(dtype),
-                                                    _stream())
-    st = _timed("cft_upsample_add", 0.0, (5.0 if want_sum else 4.0) * B * H * W * C * out0.element_size(), fn)
-    _lib.check(st, "cft_gpt_upsample_add2" if (va, ha) == (8, 8) else "cft_gpt_upsample_add2_grid")
+    fn, label, grid_args = _grid_entry(lib, "cft_gpt_upsample_add2", va, ha)
+    st = _timed("cft_upsample_add", 0.0, (5.0 if want_sum else 4.0) * B * H * W * C * out0.element_size(),
+                lambda: fn(tokens.data_ptr(), base0.data_ptr(), ldb0, 0, base1.data_ptr(), ldb1, 0, out0.data_ptr(), C, 0, out1.data_ptr(), C, 0,
+                           sp, lds, 0, B, H, W, C, *grid_args, _dt(dtype), _stream()))
+    _lib.check(st, label)
     return out0, out1, sum_out
 
 

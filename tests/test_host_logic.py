@@ -117,15 +117,107 @@ def test_pack_conv_layout(dtype):
 
 
 def test_c_abi_exports_every_declared_symbol():
-    """The shared library must load (no GPU needed) and export exactly what include/cft_hip.h declares."""
-    lib = _lib.load()
-    assert lib.cft_abi_version() == _lib.ABI_VERSION
+    """include/cft_hip.h is the only description of the ABI: _lib.SIGNATURES is parsed from it.  No prototype is skipped by the parser,
+    the built library (loads without a GPU) exports every declared name and defines no ``cft_*`` symbol the header does not declare, and
+    the parsed types of a few entry points equal the literal ones written out here."""
+    import shutil
+    import subprocess
+    c = ctypes
+    vp, i, l, f, ull = c.c_void_p, c.c_int, c.c_long, c.c_float, c.c_ulonglong
     header = open(os.path.join(ROOT, "include", "cft_hip.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|long|const char\*)\s+(cft_\w+)\s*\(", header, re.M))
-    assert declared == set(_lib.SIGNATURES) | {"cft_last_error"}, declared ^ (set(_lib.SIGNATURES) | {"cft_last_error"})
+    stripped = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
+    declared = re.findall(r"\b(cft_\w+)\s*\(", stripped)
+    assert len(declared) == len(set(declared)) == len(_lib.SIGNATURES) and set(declared) == set(_lib.SIGNATURES)
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(raw, name), name
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+        exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("cft_")}
+        assert exported and exported <= set(declared), exported - set(declared)
+    sig = {k: (r, list(a)) for k, (r, a) in _lib.SIGNATURES.items()}
+    assert sig["cft_conv2d"] == (i, [vp] * 5 + [i] * 18 + [vp])
+    assert sig["cft_attention"] == (i, [vp, vp, i, i, i, i, i, f, ull, vp])
+    assert sig["cft_to_nhwc"] == (i, [vp, i, l, l, l, l, vp, i, i, i, i, i, i, i, i, vp])
+    assert sig["cft_abi_version"] == (i, []) and sig["cft_last_error"] == (c.c_char_p, [])
+    assert sorted(k for k, (r, _) in sig.items() if r is l) == [
+        "cft_batchnorm_train_workspace", "cft_eval_ap_workspace_bytes", "cft_eval_match_workspace_bytes", "cft_loss_workspace_bytes",
+        "cft_loss_workspace_offsets"]
+    assert all(r is i for k, (r, _) in sig.items() if r is not l and k != "cft_last_error")
+    macro = int(re.search(r"^#define\s+CFT_ABI_VERSION\s+(\d+)\s*$", header, re.M).group(1))
+    lib = _lib.load()
+    assert _lib.ABI_VERSION == lib.cft_abi_version() == macro
+    assert lib.cft_abi_version.restype is i and lib.cft_loss_workspace_bytes.restype is l and lib.cft_conv2d.argtypes == sig["cft_conv2d"][1]
+    assert (_lib.CFT_BF16, _lib.CFT_F32, _lib.CFT_F16, _lib.ACT_NONE, _lib.ACT_SILU, _lib.ACT_GELU) == (0, 1, 2, 0, 1, 2)
+
+
+def test_header_parser_on_literal_snippets():
+    """_lib.parse_header on the constructs include/cft_hip.h uses (and one it must refuse): multi-line prototypes, const qualifiers,
+    unsigned long long, (void), commented-out prototypes, enumerators and the version macro; an unknown type raises, it is never
+    defaulted to int."""
+    c = ctypes
+    sigs, consts = _lib.parse_header("""
+        /* int cft_gone(int a); */
+        // long cft_gone_too(void);
+        #define CFT_ABI_VERSION 7
+        enum { CFT_A = 0, CFT_B = -2 /* int cft_in_enum(int a); */ };
+        int cft_probe(void);
+        const char* cft_text(void);
+        const char *cft_text2( void );
+        long cft_many(const void* x, const float* const* pp, int n,   /* a comment, with commas, inside */
+                      long stride, float eps,
+                      unsigned long long seed, const int flag,
+                      unsigned char* bytes, void* stream);
+        int cft_none();
+    """)
+    assert consts == {"CFT_ABI_VERSION": 7, "CFT_A": 0, "CFT_B": -2}
+    assert list(sigs) == ["cft_probe", "cft_text", "cft_text2", "cft_many", "cft_none"]
+    assert sigs["cft_probe"] == (c.c_int, []) and sigs["cft_none"] == (c.c_int, [])
+    assert sigs["cft_text"] == (c.c_char_p, []) and sigs["cft_text2"] == (c.c_char_p, [])
+    assert sigs["cft_many"] == (c.c_long, [c.c_void_p, c.c_void_p, c.c_int, c.c_long, c.c_float, c.c_ulonglong, c.c_int, c.c_void_p, c.c_void_p])
+    for bad, word in (("int cft_bad(double x);", "cft_bad"), ("int cft_bad2(int a, unsigned b);", "cft_bad2"), ("int cft_bad3(long long n);", "cft_bad3"),
+                      ("int cft_bad4(size_t n);", "cft_bad4"), ("int cft_bad5(int);", "cft_bad5"), ("int cft_bad6(int a,);", "cft_bad6"),
+                      ("double cft_bad7(int a);", "cft_bad7"), ("unsigned cft_bad8(void);", "cft_bad8")):
+        with pytest.raises(ValueError, match=word + ":"):
+            _lib.parse_header(bad)
+
+
+class _OnGpu(torch.Tensor):
+    """A meta tensor that says it lives on the GPU: the tensor forms of the eligibility predicates refuse anything else, and they only
+    read its shape, strides and dtype."""
+    is_cuda = True
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+def test_chain_predicates_tensor_and_geometry_forms_agree(dtype):
+    """ops.conv2d_chain_ok / conv2d_chain_res_ok (tensor) are adapters of their ``_geometry`` forms: the same answers for dense NHWC
+    inputs, channel slices of a wider buffer (ldx, up to the launcher's 2^31-element limit on the buffer extent), a plain NCHW tensor
+    (converted to dense first: ldx = cin), small and large pixel counts; anything that is not a 4-D GPU tensor of pk1.cin channels is
+    refused by the tensor forms."""
+    pk = lambda n, cin, k, s=1: ops.pack_conv(torch.zeros(n, cin, k, k), None, torch.bfloat16, s=s)      # noqa: E731
+    pairs = [(pk(256, 256, 3), pk(256, 256, 1)), (pk(256, 128, 3, 2), pk(256, 256, 1)), (pk(128, 64, 3, 2), pk(128, 128, 1)),
+             (pk(256, 256, 3), pk(512, 256, 1)), (pk(256, 256, 3), pk(256, 256, 3))]
+    seen = set()
+    for pk1, pk2 in pairs:
+        for B, H, W, ld in ((64, 40, 40, None), (8, 40, 40, None), (31, 40, 40, None), (32, 40, 40, 512), (2, 9, 7, None),
+                            (64, 640, 640, None), (64, 640, 640, 2 * pk1.cin), (1, 193, 256, 320)):
+            x = torch.empty((B, H, W, ld or pk1.cin), dtype=dtype, device="meta").permute(0, 3, 1, 2)[:, :pk1.cin].as_subclass(_OnGpu)
+            want = ops.conv2d_chain_ok_geometry(B, H, W, dtype, pk1, pk2, ldx=ld)
+            assert ops.conv2d_chain_ok(x, pk1, pk2) is want
+            for any_size in (False, True):
+                want_res = ops.conv2d_chain_res_ok_geometry(B, H, W, dtype, pk1, pk2, any_size=any_size, ldx=ld)
+                assert ops.conv2d_chain_res_ok(x, pk1, pk2, any_size=any_size) is want_res
+                seen.add((want, want_res))
+                Ho, Wo = ops.conv_out_size(H, W, pk1.k, pk1.s)
+                assert want_res == (want and pk1.n == 256 and (any_size or B * Ho * Wo >= ops.CHAIN_RES_MIN_ROWS))
+        nchw = torch.empty((4, pk1.cin, 40, 40), dtype=dtype, device="meta").as_subclass(_OnGpu)
+        assert ops.conv2d_chain_ok(nchw, pk1, pk2) is ops.conv2d_chain_ok_geometry(4, 40, 40, dtype, pk1, pk2)
+        assert ops.conv2d_chain_res_ok(nchw, pk1, pk2, any_size=True) is ops.conv2d_chain_res_ok_geometry(4, 40, 40, dtype, pk1, pk2, any_size=True)
+        for not_x in (torch.empty((4, pk1.cin, 40, 40), dtype=dtype), torch.empty((4, pk1.cin + 8, 40, 40), dtype=dtype, device="meta").as_subclass(_OnGpu),
+                      torch.empty((pk1.cin, 40, 40), dtype=dtype, device="meta").as_subclass(_OnGpu), None):
+            assert ops.conv2d_chain_ok(not_x, pk1, pk2) is False and ops.conv2d_chain_res_ok(not_x, pk1, pk2, any_size=True) is False
+    assert seen == ({(False, False)} if dtype == torch.float32 else {(True, True), (True, False), (False, False)})
+    assert ops.conv_out_size(640, 641, 3, 2) == (320, 321) and ops.conv_out_size(20, 20, 1, 1) == (20, 20) and ops.conv_out_size(9, 7, 5, 2) == (5, 4)
 
 
 def test_conv2d_chain_eligibility_is_a_host_decision():
