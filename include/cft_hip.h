@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bump with every change of a prototype below (history: csrc/runtime.hip).  The Python binding reads this line, the enums and
  * every prototype from this file: it is the only description of the ABI. */
-#define CFT_ABI_VERSION 14
+#define CFT_ABI_VERSION 15
 
 enum { CFT_BF16 = 0, CFT_F32 = 1, CFT_F16 = 2 };
 enum { CFT_ACT_NONE = 0, CFT_ACT_SILU = 1, CFT_ACT_GELU = 2 };
@@ -369,6 +369,37 @@ int cft_eval_match(const float* dets, const int* counts, int B, int max_det, con
 long cft_eval_ap_workspace_bytes(long n, int nc);
 int cft_eval_ap(const unsigned short* tp_bits, const float* conf, const int* pcls, long n, int niou, const int* label_hist, int nc,
                 const double* px, const double* x, void* workspace, long workspace_bytes, double* out, void* stream);
+
+/*
+ * cft_eval_confusion replaces ConfusionMatrix.process_batch (utils/metrics.py:119-157) as test.py:193-194 feeds it, for a whole
+ * batch: the grouping launch of cft_eval_match, then one workgroup per image.  An image counts only if it has a label and an
+ * NMS detection (test.py:140-143, :186).  Detections are kept if conf > conf_thres, classes are truncated toward zero (.int()),
+ * the detection class is 0 with single_cls.  Pairs with box_iou > iou_thres (float32, utils/general.py:422-444) are candidates;
+ * each detection keeps its highest-IoU label, then each label its highest-IoU detection among those that kept it (the two
+ * argsort / np.unique passes of :138-141); exactly equal IoUs, which numpy's unstable argsort leaves open, go to the lowest
+ * label index, then to the lowest detection row.  A matched label adds 1 at [detection class, label class], any other label at
+ * [nc, label class], a kept detection in no match at [its class, nc] - the last only if the image has a match (`if n:`, :154).
+ *   dets, counts, targets, img_h, img_w, geom : as for cft_eval_match
+ *   native != 0  : dets and targets columns 2..5 are native-space xyxy already (process_batch's own arguments); geom unused
+ *   matrix       : int64 [(nc + 1) * (nc + 1)], row = predicted class, column = true class, ACCUMULATED into (device)
+ *   flag         : int [1] (device), bits OR-ed in: 1 = a label class outside [0, nc), 2 = a detection class outside [0, nc);
+ *                  such labels / detections are not counted.  A matched label whose detection has a bad class is dropped
+ *                  altogether (not counted as background), and its match still enables the image's leftover-detection pass
+ * workspace: >= the size cft_eval_confusion_workspace_bytes stores in *bytes (host), 256-byte aligned.  Integer atomics only:
+ * the result does not depend on scheduling.  No allocation, no synchronisation.
+ */
+int cft_eval_confusion_workspace_bytes(int B, int nt, int max_det, long* bytes);
+int cft_eval_confusion(const float* dets, const int* counts, int B, int max_det, const float* targets, int nt, int img_h, int img_w,
+                       const float* geom, float conf_thres, float iou_thres, int single_cls, int native, int nc, void* workspace,
+                       long workspace_bytes, long long* matrix, int* flag, void* stream);
+
+/*
+ * cft_eval_export computes what test.py writes about each detection, float32, one rounding per operation in the reference's order:
+ *   out [B, max_det, 16] : x1 y1 x2 y2 in native space (scale_coords, test.py:148-149) | conf, cls (0 with single_cls), valid (1 / 0), 0 |
+ *                          xyxy2xywh / (w0, h0, w0, h0), the save_txt box (test.py:153-155) | left, top, w, h, the save_json box (:176-177)
+ * Slots r >= counts[b] are zero.  out must be 16-byte aligned.  One launch, no allocation, no synchronisation.
+ */
+int cft_eval_export(const float* dets, const int* counts, int B, int max_det, const float* geom, int single_cls, float* out, void* stream);
 
 /*
  * ComputeLoss of the reference (utils/loss.py:88-216) and its gradient with respect to the head outputs.

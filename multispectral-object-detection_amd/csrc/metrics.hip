@@ -1,10 +1,11 @@
 // mAP statistics of the reference's test.py on the GPU (the step after batched NMS):
 //   cft_eval_match  the per-image matching of detections to labels (test.py:132-218), one workgroup per image;
-//   cft_eval_ap     ap_per_class (utils/metrics.py:18-108) over all accumulated statistics.
+//   cft_eval_ap     ap_per_class (utils/metrics.py:18-108) over all accumulated statistics;
+// (cft_eval_confusion and cft_eval_export are in confusion.hip; what both files share is in metrics_common.h.)
 // Every rule follows the reference line by line; the numerics are float32 where the reference computes on tensors
 // (box transforms, IoU) and float64 where it computes in numpy (curves, AP).  No float atomics anywhere: every
 // result is the same run to run.
-#include "cft_common.h"
+#include "metrics_common.h"
 
 #pragma clang fp contract(off)   // the reference's float ops are separate roundings: no fused multiply-adds here
 
@@ -14,88 +15,14 @@ struct IouV { float v[EVAL_MAX_IOU]; };
 // ---------------------------------------------------------------------------------------------------------------------
 // (a) matching
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int MATCH_THREADS = 256;
-constexpr int MATCH_LDS_LABELS = 1024;      // labels of one image kept in LDS; more are read from the workspace
-
-// Workspace of cft_eval_match: grouped label records (box, class, winner row) and per-image label ranges.
-struct MatchWs {
-  float4* box;   // [nt] native-space xyxy
-  int* cls;      // [nt] class (-1: not an integer class; never matches)
-  int* win;      // [nt] lowest row that claims the label (global-memory path only)
-  int* off;      // [B] first grouped label of each image
-  int* cnt;      // [B] labels of each image
-};
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline size_t match_ws_layout(int B, int nt, char* base, MatchWs* w) {
-  size_t o = 0;
-  const size_t n = nt > 0 ? (size_t)nt : 1;
-  if (w) w->box = (float4*)(base + o);
-  o = align256(o + n * 16);
-  if (w) w->cls = (int*)(base + o);
-  o = align256(o + n * 4);
-  if (w) w->win = (int*)(base + o);
-  o = align256(o + n * 4);
-  if (w) w->off = (int*)(base + o);
-  o = align256(o + (size_t)B * 4);
-  if (w) w->cnt = (int*)(base + o);
-  o = align256(o + (size_t)B * 4);
-  return o;
-}
-
-// targets[:, 0] as an image index: exactly an integer in [0, B), else the label belongs to no image (test.py:136 compares with ==)
-__device__ __forceinline__ int label_image(float v, int B) {
-  if (!(v >= 0.f) || !(v < (float)B)) return -1;
-  const int b = (int)v;
-  return (float)b == v ? b : -1;
-}
-
-struct Geom { float h0, w0, gain, padw, padh; };
-
-// scale_coords (utils/general.py:353-366) + clip_coords (:369-374) on one xyxy box, float32 like ATen
-__device__ __forceinline__ float4 scale_box(float x1, float y1, float x2, float y2, const Geom& g) {
-  x1 = x1 - g.padw; x2 = x2 - g.padw;
-  y1 = y1 - g.padh; y2 = y2 - g.padh;
-  x1 = x1 / g.gain; y1 = y1 / g.gain; x2 = x2 / g.gain; y2 = y2 / g.gain;
-  x1 = fminf(fmaxf(x1, 0.f), g.w0); x2 = fminf(fmaxf(x2, 0.f), g.w0);
-  y1 = fminf(fmaxf(y1, 0.f), g.h0); y2 = fminf(fmaxf(y2, 0.f), g.h0);
-  return make_float4(x1, y1, x2, y2);
-}
-
-__device__ __forceinline__ Geom load_geom(const float* geom, int b) {
-  const float* g = geom + (long)b * 5;
-  Geom r;
-  r.h0 = g[0]; r.w0 = g[1]; r.gain = g[2]; r.padw = g[3]; r.padh = g[4];
-  return r;
-}
-
-// Block-wide exclusive prefix sum of one int per thread (MATCH_THREADS threads); returns the block total through *total.
-__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int* total) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_w[wave] = x;
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int w = 0; w < MATCH_THREADS / 64; ++w) {
-    const int c = s_w[w];
-    if (w < wave) before += c;
-    all += c;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
-
 // Stable grouping of the labels by image (one workgroup per image): image b's labels keep their order in `targets` and
 // land at [off[b], off[b] + cnt[b]) of the workspace, transformed to native-space xyxy (test.py:136, :201-202).  Also adds the
-// image's labels to the class histogram (slot nc counts labels whose class is not an integer in [0, nc)).
+// image's labels to the class histogram (slot nc counts labels whose class is not an integer in [0, nc)).  `key` (optional)
+// is the per-label selection word of cft_eval_confusion, cleared here.
 __global__ void __launch_bounds__(MATCH_THREADS) eval_group_kernel(const float* __restrict__ targets, int nt, int B, float img_h, float img_w,
                                                                    const float* __restrict__ geom, MatchWs ws, int* __restrict__ label_hist,
-                                                                   int nc, int* __restrict__ tcls_out, int* __restrict__ nl_out) {
+                                                                   int nc, int* __restrict__ tcls_out, int* __restrict__ nl_out, int mode,
+                                                                   unsigned long long* __restrict__ key) {
   __shared__ int s_w[MATCH_THREADS / 64];
   const int b = blockIdx.x, tid = threadIdx.x;
   int before = 0, mine = 0;
@@ -108,7 +35,7 @@ __global__ void __launch_bounds__(MATCH_THREADS) eval_group_kernel(const float* 
   block_excl_scan(before, s_w, &tb);
   block_excl_scan(mine, s_w, &tm);
   if (tid == 0) { ws.off[b] = tb; ws.cnt[b] = tm; if (nl_out) nl_out[b] = tm; }
-  const Geom g = load_geom(geom, b);
+  const Geom g = (mode & GROUP_NATIVE) ? Geom{0.f, 0.f, 1.f, 0.f, 0.f} : load_geom(geom, b);
   int run = 0;
   for (int i0 = 0; i0 < nt; i0 += MATCH_THREADS) {
     const int i = i0 + tid;
@@ -119,10 +46,15 @@ __global__ void __launch_bounds__(MATCH_THREADS) eval_group_kernel(const float* 
       const float* t = targets + (long)i * 6;
       const int pos = tb + run + rank;
       // targets[:, 2:] *= [W, H, W, H] (test.py:125), xywh2xyxy (utils/general.py:299-306), scale_coords
-      const float x = t[2] * img_w, y = t[3] * img_h, w = t[4] * img_w, h = t[5] * img_h;
-      ws.box[pos] = scale_box(x - w / 2.f, y - h / 2.f, x + w / 2.f, y + h / 2.f, g);
+      if (mode & GROUP_NATIVE) {
+        ws.box[pos] = make_float4(t[2], t[3], t[4], t[5]);
+      } else {
+        const float x = t[2] * img_w, y = t[3] * img_h, w = t[4] * img_w, h = t[5] * img_h;
+        ws.box[pos] = scale_box(x - w / 2.f, y - h / 2.f, x + w / 2.f, y + h / 2.f, g);
+      }
       const float cf = t[1];
-      const int c = (cf >= 0.f && cf < 2147483520.f && (float)(int)cf == cf) ? (int)cf : -1;
+      const int c = (mode & GROUP_TRUNC_CLS) ? trunc_class(cf) : ((cf >= 0.f && cf < 2147483520.f && (float)(int)cf == cf) ? (int)cf : -1);
+      if (key) key[pos] = 0ull;
       ws.cls[pos] = c;
       ws.win[pos] = 0x7fffffff;
       if (tcls_out) tcls_out[pos] = c;
@@ -130,15 +62,6 @@ __global__ void __launch_bounds__(MATCH_THREADS) eval_group_kernel(const float* 
     }
     run += tot;
   }
-}
-
-// box_iou (utils/general.py:422-444) of one prediction with one label, float32: inter / (area1 + area2 - inter)
-__device__ __forceinline__ float box_iou1(const float4& p, float pa, const float4& t) {
-  const float iw = fmaxf(fminf(p.z, t.z) - fmaxf(p.x, t.x), 0.f);
-  const float ih = fmaxf(fminf(p.w, t.w) - fmaxf(p.y, t.y), 0.f);
-  const float inter = iw * ih;
-  const float ta = (t.z - t.x) * (t.w - t.y);
-  return inter / (pa + ta - inter);
 }
 
 // Best label of the prediction's class (test.py:207 `box_iou(...).max(1)`): first index on ties, a NaN wins like torch.max.
@@ -219,6 +142,13 @@ __global__ void __launch_bounds__(MATCH_THREADS) eval_match_kernel(const float* 
   }
 }
 
+int eval_group_launch(const float* targets, int nt, int B, float img_h, float img_w, const float* geom, MatchWs ws, int* label_hist, int nc,
+                      int* tcls, int* nl, int mode, unsigned long long* key, hipStream_t stream) {
+  hipLaunchKernelGGL(eval_group_kernel, dim3(B), dim3(MATCH_THREADS), 0, stream, targets, nt, B, img_h, img_w, geom, ws, label_hist, nc, tcls, nl,
+                     mode, key);
+  return cft_check_launch("eval_group_kernel");
+}
+
 extern "C" long cft_eval_match_workspace_bytes(int B, int nt) {
   if (B <= 0 || nt < 0) return -1;
   return (long)match_ws_layout(B, nt, nullptr, nullptr);
@@ -239,9 +169,7 @@ extern "C" int cft_eval_match(const float* dets, const int* counts, int B, int m
   for (int k = 0; k < EVAL_MAX_IOU; ++k) iv.v[k] = k < niou ? iouv_host[k] : 2.f;
   MatchWs w;
   match_ws_layout(B, nt, (char*)workspace, &w);
-  hipLaunchKernelGGL(eval_group_kernel, dim3(B), dim3(MATCH_THREADS), 0, as_stream(stream), targets, nt, B, (float)img_h, (float)img_w, geom, w,
-                     label_hist, nc, tcls, nl);
-  int st = cft_check_launch("eval_group_kernel");
+  int st = eval_group_launch(targets, nt, B, (float)img_h, (float)img_w, geom, w, label_hist, nc, tcls, nl, 0, nullptr, as_stream(stream));
   if (st != CFT_OK) return st;
   hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(MATCH_THREADS), 0, as_stream(stream), dets, counts, max_det, geom, iv, niou, single_cls, w,
                      correct, tp_bits, conf, pcls);

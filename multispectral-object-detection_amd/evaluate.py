@@ -3,27 +3,78 @@
     from msod_amd.evaluate import evaluate
     (mp, mr, map50, map75, map), maps = evaluate(model, dataloader, nc)
     (mp, mr, map50, map75, map, box, obj, cls), maps = evaluate(model, dataloader, nc, compute_loss=ComputeLoss(model))
+    results, maps, extras = evaluate(model, dataloader, nc, confusion=True, save_txt=True, save_json=True, save_dir="runs/val")
 
 Per batch: the forward on the uint8 views (the /255 is fused into Focus), ``batched_nms(multi_label=True,
 agnostic=single_cls)`` and ``DetectionEvaluator.update`` - no host synchronisation beyond the iterator's own.  One
 synchronisation at the end computes the statistics.  With ``compute_loss`` (``utils.loss.ComputeLoss``) the validation
-loss is accumulated on the device too, as test.py does (:121-123, :295).  Plots, save_txt / save_json and the confusion
-matrix are not computed.
+loss is accumulated on the device too, as test.py does (:121-123, :295).
+
+The rest of what ``python test.py`` gives is behind keywords that are off by default (the default path is unchanged):
+
+* ``confusion``    the (nc+1) x (nc+1) confusion matrix of test.py's ``plots=True`` (``utils.metrics.ConfusionMatrix``: its
+                   rules, quirks and tie rule are described there), accumulated on the device, still without synchronisation;
+* ``save_txt``     one ``save_dir/labels/<stem>.txt`` per image with detections, a line ``class x y w h`` (normalised, ``%g``) per
+                   detection, with the confidence appended if ``save_conf`` (test.py:152-158).  Lines are appended, as there;
+* ``save_hybrid``  the batch's labels join the NMS candidates as a-priori rows (test.py:126-129, utils/general.py:480-487); implies
+                   ``save_txt`` (test.py:336).  The rows are built on the host from the dataloader's CPU targets;
+* ``save_json``    the COCO-style list of test.py:173-182, returned as ``jdict`` and, with a ``save_dir``, written to
+                   ``save_dir/predictions.json``.
+
+The values written come from one kernel (``cft_eval_export``) and one device-to-host copy per batch: the only added
+synchronisation, and only when a save option is on.  PR / F1 curve plots, wandb logging and pycocotools scoring are not done.
 """
+import json
+from pathlib import Path
+
 import torch
 
 from .utils.general import batched_nms
-from .utils.metrics import DetectionEvaluator
+from .utils.metrics import DetectionEvaluator, export_batch, export_rows, json_entry, txt_line
 
 
-def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None):
+def _apriori_rows(targets, B, no, H, W):
+    """save_hybrid: the labels of a batch as pre-NMS rows [B, L, no] on the host (utils/general.py:480-487: box in letterbox pixels,
+    obj = 1, one-hot class), L = the most labels of one image; images with fewer get obj = 0 rows, which the conf filter drops."""
+    if targets.device.type != "cpu":
+        raise ValueError("evaluate: save_hybrid builds the a-priori rows on the host and needs the dataloader's CPU targets")
+    t = targets.float()
+    px = t[:, 2:] * torch.tensor([W, H, W, H], dtype=torch.float32)       # test.py:126, float32 as there
+    idx = [(t[:, 0] == b).nonzero().view(-1) for b in range(B)]            # test.py:127
+    L = max(len(i) for i in idx)
+    if L == 0:
+        return None
+    cls = t[:, 1].long()
+    if len(cls) and (int(cls.min()) < 0 or int(cls.max()) >= no - 5):
+        raise ValueError(f"evaluate: save_hybrid labels have a class outside [0, {no - 5})")
+    extra = torch.zeros((B, L, no), dtype=torch.float32)
+    for b, i in enumerate(idx):
+        k = len(i)
+        extra[b, :k, :4] = px[i]
+        extra[b, :k, 4] = 1.0
+        extra[b, torch.arange(k), cls[i] + 5] = 1.0
+    return extra
+
+
+def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None, confusion=False,
+             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None):
     """batches: an iterable of ``(img6_uint8 [B, 6, H, W], targets [nt, 6], paths, shapes)`` as test.py's dataloader yields.
     Returns test.py's ``((mp, mr, map50, map75, map), maps)``; with ``compute_loss``, test.py's
-    ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches."""
+    ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches.
+
+    With any of ``confusion``, ``save_txt``, ``save_hybrid``, ``save_json`` (module docstring) a third element follows:
+    ``{"confusion_matrix": (nc+1, nc+1) float64 numpy array or None, "jdict": list of entries or None}``."""
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model must be on the GPU (this package has no CPU path)")
-    ev = DetectionEvaluator(1 if single_cls else nc, single_cls)          # test.py:74
+    save_txt = save_txt or save_hybrid                                     # test.py:336
+    extras = confusion or save_txt or save_json
+    if save_txt:
+        if save_dir is None:
+            raise ValueError("evaluate: save_txt / save_hybrid need a save_dir")
+        (Path(save_dir) / 'labels').mkdir(parents=True, exist_ok=True)    # test.py:54
+    jdict = [] if save_json else None
+    ev = DetectionEvaluator(1 if single_cls else nc, single_cls, confusion=confusion)          # test.py:74, :97
     loss = torch.zeros(3, device=device) if compute_loss is not None else None
     nb = 0
     for img, targets, paths, shapes in batches:
@@ -37,12 +88,30 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
             out = res[0]
             if compute_loss is not None:                                   # test.py:121-123, normalised targets
                 loss += compute_loss([x.float().contiguous() for x in res[1]], targets)[1][:3]
+            if save_hybrid:
+                extra = _apriori_rows(targets, img.shape[0], out.shape[2], H, W)
+                if extra is not None:
+                    out = torch.cat((out.float(), extra.pin_memory().to(device, non_blocking=True)), 1)
             dets, counts = batched_nms(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
         ev.update(dets, counts, targets, (H, W), shapes)
+        if save_txt or save_json:
+            for stem, rows in export_rows(export_batch(dets, counts, (H, W), shapes, single_cls), paths):
+                if save_txt:
+                    with open(Path(save_dir) / 'labels' / (stem + '.txt'), 'a') as f:
+                        f.writelines(txt_line(r[5], r[8:12], r[4] if save_conf else None) for r in rows)
+                if save_json:
+                    jdict.extend(json_entry(stem, r[5], r[12:16], r[4]) for r in rows)
         nb += 1
-    if compute_loss is None:
-        return ev.compute().as_test_tuple()
-    results, maps = ev.compute().as_test_tuple()
-    losses = (loss.cpu() / nb).tolist() if nb else [0.0, 0.0, 0.0]          # test.py:295
-    compute_loss.check()
-    return (*results, *losses), maps
+    res = ev.compute()
+    results, maps = res.as_test_tuple()
+    if compute_loss is not None:
+        losses = (loss.cpu() / nb).tolist() if nb else [0.0, 0.0, 0.0]          # test.py:295
+        compute_loss.check()
+        results = (*results, *losses)
+    if not extras:
+        return results, maps
+    if save_json and save_dir is not None and len(jdict):                      # test.py:262-268
+        Path(save_dir).mkdir(parents=True, exist_ok=True)
+        with open(Path(save_dir) / 'predictions.json', 'w') as f:
+            json.dump(jdict, f)
+    return results, maps, {"confusion_matrix": res.confusion_matrix, "jdict": jdict}

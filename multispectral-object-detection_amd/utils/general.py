@@ -87,6 +87,25 @@ def xywh2xyxy(x):
     return y
 
 
+def xyxy2xywh(x):
+    """[x1, y1, x2, y2] -> [x centre, y centre, w, h] (reference utils/general.py:289-296); tiny, used by callers on results."""
+    y = x.clone()
+    y[..., 0] = (x[..., 0] + x[..., 2]) / 2
+    y[..., 1] = (x[..., 1] + x[..., 3]) / 2
+    y[..., 2] = x[..., 2] - x[..., 0]
+    y[..., 3] = x[..., 3] - x[..., 1]
+    return y
+
+
+def box_iou(box1, box2):
+    """IoU matrix [N, M] of xyxy boxes box1 [N, 4] and box2 [M, 4] (reference utils/general.py:422-444), for callers working on
+    results; the evaluation kernels compute their IoUs themselves."""
+    area1 = (box1[:, 2] - box1[:, 0]) * (box1[:, 3] - box1[:, 1])
+    area2 = (box2[:, 2] - box2[:, 0]) * (box2[:, 3] - box2[:, 1])
+    inter = (torch.min(box1[:, None, 2:], box2[:, 2:]) - torch.max(box1[:, None, :2], box2[:, :2])).clamp(0).prod(2)
+    return inter / (area1[:, None] + area2 - inter)
+
+
 def clip_coords(boxes, img_shape):
     """Clip xyxy boxes to the image (height, width), in place (reference utils/general.py:369-374)."""
     boxes[:, 0].clamp_(0, img_shape[1])

@@ -7,11 +7,25 @@ matched detection) and then runs ``ap_per_class`` (``utils/metrics.py:18-108``) 
 * ``match_batch``          one batch's ``batched_nms`` output against its labels (``cft_eval_match``);
 * ``ap_per_class``         the reference's function, same signature and return value (``cft_eval_ap``);
 * ``DetectionEvaluator``   accumulates batches on the device without host synchronisation and computes
-                           ``test.py``'s metrics with one synchronisation.
+                           ``test.py``'s metrics with one synchronisation;
+* ``ConfusionMatrix``      the reference's class (``utils/metrics.py:111-183``): ``process_batch`` per image as there, and a
+                           batched ``update`` on the ``batched_nms`` output (``cft_eval_confusion``), accumulated on the device;
+* ``export_batch``         the box values of ``save_txt`` / ``save_json`` for every detection slot (``cft_eval_export``);
+                           ``txt_line`` and ``json_entry`` format them as ``test.py:156-158`` and ``:179-182`` do.
 
 Every rule is the reference's: float32 box arithmetic as ATen does it, float64 curves as numpy does them.
+
+The confusion matrix keeps the reference's quirks: only an image with labels and NMS detections counts (``test.py:140-143``,
+``:186``); detections are kept if ``conf > 0.25`` and pairs are candidates if ``iou > 0.45`` (both strict); each detection
+keeps its highest-IoU label, then each label its highest-IoU detection among those that kept it, whatever their classes;
+unmatched kept detections count as background only in an image that has a match (``if n:``, ``utils/metrics.py:154``); without
+a kept detection every label of the image counts as background.  The reference leaves exactly equal IoUs to numpy's unstable
+argsort; here the lowest label index wins, then the lowest detection index.  A class outside ``[0, nc)`` is not counted and
+makes ``.matrix`` raise.
 """
+import ctypes
 from dataclasses import dataclass
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -216,6 +230,181 @@ def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, save_dir='.', names
     return p[ap_class], r[ap_class], ap[ap_class], f1[ap_class], ap_class.astype(np.int32)
 
 
+def _geom_device(shapes, img_hw, B, device, what):
+    if len(shapes) != B:
+        raise ValueError(f"{what}: {len(shapes)} shapes for a batch of {B} images")
+    if int(img_hw[0]) <= 0 or int(img_hw[1]) <= 0:
+        raise ValueError(f"{what}: bad image size {img_hw}")
+    return _to_device(geometry(shapes, img_hw), device)
+
+
+class ConfusionMatrix:
+    """The reference's ConfusionMatrix (utils/metrics.py:111-183) on the GPU: ``matrix[predicted class, true class]`` with row and
+    column ``nc`` for the background, as ``process_batch`` fills it (the rules and the tie rule are in the module docstring).
+    Counts accumulate in an int64 matrix on the device; neither ``process_batch`` nor ``update`` synchronises with the host."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45):
+        if int(nc) < 1 or int(nc) > 32767:
+            raise ValueError(f"ConfusionMatrix: nc must be in [1, 32767], got {nc}")
+        self.nc = int(nc)  # number of classes
+        self.conf = conf
+        self.iou_thres = iou_thres
+        self._m = self._flag = None
+
+    def reset(self):
+        """Zero the counts and the bad-class flag (in place on the device, no synchronisation)."""
+        if self._m is not None:
+            self._m.zero_()
+            self._flag.zero_()
+
+    def _launch(self, dets, counts, targets, H, W, geom, single_cls, native):
+        device = dets.device
+        if self._m is None:
+            self._m = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int64, device=device)
+            self._flag = torch.zeros((1,), dtype=torch.int32, device=device)
+        elif device != self._m.device:
+            raise ValueError(f"ConfusionMatrix: batch on {device}, earlier batches on {self._m.device}")
+        B, max_det, nt = dets.shape[0], dets.shape[1], targets.shape[0]
+        lib = _lib.load()
+        nbytes = ctypes.c_long(0)
+        _lib.check(lib.cft_eval_confusion_workspace_bytes(B, nt, max_det, ctypes.byref(nbytes)), "cft_eval_confusion_workspace_bytes")
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=device)
+        st = lib.cft_eval_confusion(dets.data_ptr(), counts.data_ptr(), B, max_det, targets.data_ptr() if nt else None, nt, H, W,
+                                    geom.data_ptr() if geom is not None else None, float(self.conf), float(self.iou_thres),
+                                    int(bool(single_cls)), int(native), self.nc, ws.data_ptr(), ws.numel(), self._m.data_ptr(),
+                                    self._flag.data_ptr(), _stream())
+        _lib.check(st, "cft_eval_confusion")
+
+    def process_batch(self, detections, labels):
+        """One image, as the reference: detections [N, 6] = x1, y1, x2, y2, conf, class and labels [M, 5] = class, x1, y1, x2, y2,
+        both in native image space, tensors on the GPU.  Updates the matrix."""
+        _require_cuda(detections, "ConfusionMatrix.process_batch")
+        _require_cuda(labels, "ConfusionMatrix.process_batch")
+        if detections.dim() != 2 or detections.shape[1] != 6 or labels.dim() != 2 or labels.shape[1] != 5:
+            raise ValueError(f"ConfusionMatrix.process_batch: detections [N, 6] and labels [M, 5], got {tuple(detections.shape)} and "
+                             f"{tuple(labels.shape)}")
+        N, M = detections.shape[0], labels.shape[0]
+        if N == 0 and M == 0:
+            return
+        device = detections.device
+        dets = torch.zeros((1, max(N, 1), 6), dtype=torch.float32, device=device)
+        dets[0, :N].copy_(detections)
+        targets = torch.zeros((M, 6), dtype=torch.float32, device=device)          # image 0 | class | xyxy
+        targets[:, 1:].copy_(labels)
+        if N == 0:
+            # the reference's process_batch counts every label as background when it is handed no detection (test.py never does):
+            # a slot below the conf filter stands in, so that the image is not taken for one without NMS detections
+            dets[0, 0, 4] = float("-inf")
+        counts = _to_device(torch.tensor([max(N, 1)], dtype=torch.int32), device)
+        self._launch(dets, counts, targets, 0, 0, None, False, 1)
+
+    def update(self, dets, counts, targets, img_hw, shapes, single_cls=False):
+        """One batch, as test.py:193-194 feeds process_batch image by image: (dets, counts) from batched_nms (or
+        non_max_suppression's list with counts=None); targets [nt, 6], img_hw and shapes as for match_batch."""
+        device = dets[0].device if isinstance(dets, (list, tuple)) and len(dets) else getattr(dets, "device", None)
+        if device is None or device.type != "cuda":
+            raise RuntimeError("ConfusionMatrix.update: detections must be on the GPU (this package has no CPU path)")
+        dets, counts = _pack_dets(dets, counts, device)
+        if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.shape[1] != 6:
+            raise ValueError(f"ConfusionMatrix.update: targets must be an [nt, 6] tensor, got {getattr(targets, 'shape', type(targets))}")
+        geom = _geom_device(shapes, img_hw, dets.shape[0], device, "ConfusionMatrix.update")
+        targets = _to_device(targets.float(), device).contiguous()
+        self._launch(dets, counts, targets, int(img_hw[0]), int(img_hw[1]), geom, single_cls, 0)
+
+    @property
+    def matrix(self):
+        """(nc + 1, nc + 1) float64 numpy array, as the reference's attribute.  Synchronises once."""
+        if self._m is None:
+            return np.zeros((self.nc + 1, self.nc + 1))
+        both = torch.cat((self._m.reshape(-1), self._flag.to(torch.int64))).cpu().numpy()
+        if both[-1]:
+            what = " and ".join(w for bit, w in ((1, "labels"), (2, "detections")) if both[-1] & bit)
+            raise ValueError(f"ConfusionMatrix: {what} with a class outside [0, {self.nc}) were skipped")
+        return both[:-1].reshape(self.nc + 1, self.nc + 1).astype(np.float64)
+
+    def plot(self, save_dir='', names=()):
+        """The reference's normalised heat map (utils/metrics.py:162-179) with matplotlib alone (it uses seaborn); like there, any
+        failure (matplotlib missing, unwritable directory) is silent."""
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+            m = self.matrix
+            array = m / (m.sum(0).reshape(1, self.nc + 1) + 1E-6)  # normalize
+            array[array < 0.005] = np.nan  # don't annotate (would appear as 0.00)
+            fig, ax = plt.subplots(figsize=(12, 9), tight_layout=True)
+            im = ax.imshow(array, cmap='Blues')
+            fig.colorbar(im, ax=ax)
+            if self.nc < 30:
+                for i in range(self.nc + 1):
+                    for j in range(self.nc + 1):
+                        if not np.isnan(array[i, j]):
+                            ax.text(j, i, f"{array[i, j]:.2f}", ha="center", va="center", fontsize=8)
+            names = list(names)
+            if 0 < len(names) < 99 and len(names) == self.nc:  # apply names to ticklabels
+                ax.set_xticks(range(self.nc + 1))
+                ax.set_xticklabels(names + ['background FP'], rotation=90)
+                ax.set_yticks(range(self.nc + 1))
+                ax.set_yticklabels(names + ['background FN'])
+            ax.set_xlabel('True')
+            ax.set_ylabel('Predicted')
+            fig.savefig(Path(save_dir) / 'confusion_matrix.png', dpi=250)
+            plt.close(fig)
+        except Exception:
+            pass
+
+    def print(self):
+        m = self.matrix
+        for i in range(self.nc + 1):
+            print(' '.join(map(str, m[i])))
+
+
+EXPORT_FLOATS = 16      # per slot: xyxy | conf cls valid 0 | save_txt xywh | save_json xywh (include/cft_hip.h, cft_eval_export)
+
+
+def export_batch(dets, counts, img_hw, shapes, single_cls=False):
+    """float32 [B, max_det, 16] on the device, per detection slot of the batched_nms output: native-space xyxy | conf, class,
+    valid (1 / 0), 0 | the normalised xywh of save_txt (test.py:153-155) | the top-left xywh of save_json (:176-177)."""
+    device = getattr(dets, "device", None)
+    if device is None or device.type != "cuda":
+        raise RuntimeError("export_batch: detections must be on the GPU (this package has no CPU path)")
+    dets, counts = _pack_dets(dets, counts, device)
+    B, max_det = dets.shape[0], dets.shape[1]
+    geom = _geom_device(shapes, img_hw, B, device, "export_batch")
+    out = torch.empty((B, max_det, EXPORT_FLOATS), dtype=torch.float32, device=device)
+    st = _lib.load().cft_eval_export(dets.data_ptr(), counts.data_ptr(), B, max_det, geom.data_ptr(), int(bool(single_cls)),
+                                     out.data_ptr(), _stream())
+    _lib.check(st, "cft_eval_export")
+    return out
+
+
+def txt_line(cls, xywh, conf=None):
+    """One line of a save_txt label file (test.py:156-158): class, normalised xywh and, with save_conf, the confidence."""
+    line = (cls, *xywh, conf) if conf is not None else (cls, *xywh)
+    return ('%g ' * len(line)).rstrip() % line + '\n'
+
+
+def json_entry(stem, cls, box, score):
+    """One entry of the save_json list (test.py:175-182): box = top-left xywh in native pixels."""
+    return {'image_id': int(stem) if stem.isnumeric() else stem, 'category_id': int(cls), 'bbox': [round(x, 3) for x in box],
+            'score': round(score, 5)}
+
+
+def export_rows(export, paths):
+    """Host side of save_txt / save_json: the export buffer of one batch (one device-to-host copy) -> per image
+    (stem, rows [n, 16] as Python floats), skipping images without detections (test.py:140-143)."""
+    rows = export.cpu()
+    B = rows.shape[0]
+    if paths is None or len(paths) != B:
+        raise ValueError(f"save_txt / save_json need the image paths of the batch ({B} images)")
+    out = []
+    for b in range(B):
+        n = int(rows[b, :, 6].sum())
+        if n:
+            out.append((Path(paths[b]).stem, rows[b, :n].tolist()))
+    return out
+
+
 @dataclass
 class EvalResult:
     """test.py's metrics (:227-236, :292-294).  p, r, ap, f1, ap_class as ap_per_class returns them; nt = labels per class."""
@@ -232,6 +421,7 @@ class EvalResult:
     ap_class: np.ndarray
     nt: object
     seen: int
+    confusion_matrix: object = None     # (nc + 1, nc + 1) float64 numpy array with DetectionEvaluator(confusion=True), else None
 
     def as_test_tuple(self):
         """test.py's ``((mp, mr, map50, map75, map), maps)`` (without the validation losses)."""
@@ -240,13 +430,16 @@ class EvalResult:
 
 class DetectionEvaluator:
     """Accumulates test.py's statistics on the GPU.  ``update()`` never synchronises with the host: every batch appends its
-    B * max_det slots (empty ones are dropped later), so buffer offsets are known on the host.  ``compute()`` synchronises once."""
+    B * max_det slots (empty ones are dropped later), so buffer offsets are known on the host.  ``compute()`` synchronises once
+    (once more for the confusion matrix).  ``confusion=True`` also feeds every batch to a ``ConfusionMatrix`` (one more launch pair, still no synchronisation);
+    ``EvalResult.confusion_matrix`` then holds its matrix."""
 
-    def __init__(self, nc, single_cls=False):
+    def __init__(self, nc, single_cls=False, confusion=False):
         if int(nc) < 1 or int(nc) > 65535:
             raise ValueError(f"DetectionEvaluator: nc must be in [1, 65535], got {nc}")
         self.nc = int(nc)
         self.single_cls = bool(single_cls)
+        self.confusion = bool(confusion)
         self.device = None
         self.reset()
 
@@ -254,6 +447,12 @@ class DetectionEvaluator:
         self.n = 0
         self.seen = 0
         self._tp = self._conf = self._pcls = self._hist = None
+        if not self.confusion:
+            self.confusion_matrix = None
+        elif getattr(self, "confusion_matrix", None) is None:
+            self.confusion_matrix = ConfusionMatrix(self.nc)                               # test.py:97
+        else:
+            self.confusion_matrix.reset()
 
     def _reserve(self, device, need):
         if self.device is None or self._hist is None:
@@ -287,6 +486,8 @@ class DetectionEvaluator:
         sl = slice(self.n, self.n + k)
         _match(dets, counts, targets, img_hw, shapes, self.single_cls, self._tp[sl], self._conf[sl], self._pcls[sl], None,
                self._hist, self.nc, None, None)
+        if self.confusion_matrix is not None:
+            self.confusion_matrix.update(dets, counts, targets, img_hw, shapes, self.single_cls)
         self.n += k
         self.seen += B
 
@@ -294,6 +495,7 @@ class DetectionEvaluator:
         nc, niou = self.nc, NIOU
         maps0 = np.zeros(nc)
         empty = EvalResult(0., 0., 0., 0., 0., maps0, 0., 0., [], 0., [], torch.zeros(1), self.seen)
+        cm = empty.confusion_matrix = self.confusion_matrix.matrix if self.confusion_matrix is not None else None
         if self._hist is None:
             return empty
         out = _ap_device(self._tp, self._conf, self._pcls, self.n, niou, self._hist, nc, self.device)
@@ -313,4 +515,4 @@ class DetectionEvaluator:
         for i, c in enumerate(ap_class):
             maps[c] = apm[i]
         return EvalResult(float(mp), float(mr), float(map50), float(map75), float(map_), maps, p, r, ap, f1, ap_class.astype(np.int32),
-                          nt, self.seen)
+                          nt, self.seen, cm)

@@ -5,7 +5,11 @@
 Per 64-image batch (300 detections and 20 labels per image, 3 classes): match_batch + DetectionEvaluator.update
 versus a per-image / per-class Python loop in the style of test.py:132-218 (written here from the rules, on the
 same GPU tensors).  Then DetectionEvaluator.compute() (ap_per_class) for 1013 x 300 detections with 3 classes and
-5000 x 300 with 80 classes.  Prints one JSON line; every time ends in a device synchronisation.
+5000 x 300 with 80 classes.  The confusion / export leg times, on the same 64-image batch and alternating the sides round by
+round: update() without and with confusion=True, a per-image process_batch loop in the reference's style (written here from
+the algorithm, on GPU tensors), the two confusion launches alone, the two matching launches alone, and export_batch with its
+device-to-host copy.  Both update() legs include their evaluator's reset(): the plain one reserves its statistics buffers again,
+the confusion one also zeroes its matrix in place (nothing is allocated for it after the first round).  Prints one JSON line; every time ends in a device synchronisation.
 """
 import argparse
 import json
@@ -18,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import msod_amd  # noqa: E402,F401
-from msod_amd.utils.metrics import DetectionEvaluator, IOUV  # noqa: E402
+from msod_amd.utils.metrics import ConfusionMatrix, DetectionEvaluator, IOUV, export_batch, match_batch  # noqa: E402
 
 
 def make_batch(g, B, nd, nl, nc, H, W, dev):
@@ -83,6 +87,64 @@ def loop_stats(dets, counts, targets, img_hw, shapes):
     return stats
 
 
+def loop_confusion(dets, counts, targets, img_hw, shapes, nc, conf=0.25, iou_thres=0.45):
+    """A per-image confusion matrix in the reference's style (boolean filter, torch.where, argsort / np.unique on the host, one
+    Python loop over labels and one over detections), on GPU tensors."""
+    H, W = img_hw
+    t = targets.clone()
+    t[:, 2:] *= torch.tensor([W, H, W, H], device=dets.device)
+    matrix = np.zeros((nc + 1, nc + 1))
+    for si in range(dets.shape[0]):
+        pred = dets[si, :int(counts[si])]
+        labels = t[t[:, 0] == si, 1:]
+        if not len(pred) or not len(labels):
+            continue
+        predn = pred.clone()
+        _native(predn[:, :4], img_hw, shapes[si])
+        xy, wh = labels[:, 1:3], labels[:, 3:5]
+        tbox = _native(torch.cat([xy - wh / 2, xy + wh / 2], 1), img_hw, shapes[si])
+        d = predn[predn[:, 4] > conf]
+        gtc, dc = labels[:, 0].int(), d[:, 5].int()
+        iou = _box_iou(tbox, d[:, :4])
+        x = torch.where(iou > iou_thres)
+        if x[0].shape[0]:
+            mt = torch.cat((torch.stack(x, 1), iou[x[0], x[1]][:, None]), 1).cpu().numpy()
+            mt = mt[mt[:, 2].argsort()[::-1]]
+            mt = mt[np.unique(mt[:, 1], return_index=True)[1]]
+            mt = mt[mt[:, 2].argsort()[::-1]]
+            mt = mt[np.unique(mt[:, 0], return_index=True)[1]]
+        else:
+            mt = np.zeros((0, 3))
+        m0, m1 = mt[:, 0].astype(int), mt[:, 1].astype(int)
+        for i, gc in enumerate(gtc):
+            j = m0 == i
+            if j.sum() == 1:
+                matrix[dc[m1[j]], gc] += 1
+            else:
+                matrix[nc, gc] += 1
+        if len(mt):
+            for i, c in enumerate(dc):
+                if not (m1 == i).any():
+                    matrix[c, nc] += 1
+    return matrix
+
+
+def alternated(fns, rounds, warm=3):
+    """Median seconds of each callable, the callables taking turns round by round (drift hits every side alike)."""
+    for _ in range(warm):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[k].append(time.perf_counter() - t0)
+    return {k: float(np.median(v)) for k, v in ts.items()}
+
+
 def timed(fn, reps):
     fn()
     torch.cuda.synchronize()
@@ -114,6 +176,22 @@ def main():
     res = {"metric": "eval_bench"}
     res["update_ms_per_64"] = timed(gpu_step, a.reps * 4) * 1e3
     res["loop_ms_per_64"] = timed(lambda: loop_stats(*batch[:3], (H, W), batch[3]), 2) * 1e3
+    # confusion / export leg
+    ev_cm = DetectionEvaluator(3, confusion=True)
+    cm = ConfusionMatrix(3)
+
+    def cm_step():
+        ev_cm.reset()
+        ev_cm.update(*batch[:3], (H, W), batch[3])
+    med = alternated({"update_ms_per_64_alt": gpu_step, "update_confusion_ms_per_64": cm_step,
+                      "confusion_only_ms_per_64": lambda: cm.update(*batch[:3], (H, W), batch[3]),
+                      "match_only_ms_per_64": lambda: match_batch(*batch[:3], (H, W), batch[3]),
+                      "export_d2h_ms_per_64": lambda: export_batch(*batch[:2], (H, W), batch[3]).cpu()}, a.reps * 8)
+    res.update({k: v * 1e3 for k, v in med.items()})
+    res["confusion_loop_ms_per_64"] = timed(lambda: loop_confusion(*batch[:3], (H, W), batch[3], 3), 2) * 1e3
+    cm1 = ConfusionMatrix(3)
+    cm1.update(*batch[:3], (H, W), batch[3])
+    res["confusion_matches_loop"] = bool(np.array_equal(cm1.matrix, loop_confusion(*batch[:3], (H, W), batch[3], 3)))
     for name, n_img, nc in (("flir_1013x300_nc3", 1013, 3), ("coco_5000x300_nc80", 5000, 80)):
         ev = DetectionEvaluator(nc)
         b64 = make_batch(g, 64, 300, 20, nc, H, W, dev)
