@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bump with every change of a prototype below (history: csrc/runtime.hip).  The Python binding reads this line, the enums and
  * every prototype from this file: it is the only description of the ABI. */
-#define CFT_ABI_VERSION 15
+#define CFT_ABI_VERSION 16
 
 enum { CFT_BF16 = 0, CFT_F32 = 1, CFT_F16 = 2 };
 enum { CFT_ACT_NONE = 0, CFT_ACT_SILU = 1, CFT_ACT_GELU = 2 };
@@ -427,6 +427,38 @@ long cft_loss_workspace_offsets(int nl, int B, int na, const int* ny, const int*
 int cft_loss_backward(int nl, const float* const* p, int B, int na, const int* ny, const int* nx, int nc, int nt, const float* anchors,
                       const double* hyp, const float* grad_loss, float* const* grad, void* workspace, long workspace_bytes,
                       void* stream);
+
+/*
+ * utils/autoanchor.py of the reference (check_anchors :23-59, kmean_anchors :103-201).  All three are asynchronous, allocate nothing
+ * and use no float atomics; every result is the same run to run.  n < 2^24 labels, na <= 64 anchors, thr = 1 / anchor_t in [1/64, 1].
+ *
+ * cft_anchor_metric: x_ij = min over the two dims of min(r, 1 / r), r = wh_i / k_j (IEEE float32 divisions, bit-identical to torch on a
+ * CPU), best_i = max_j x_ij.
+ *   wh [n, 2], k [na, 2] float32 (device);  out: 8 x uint64 (device, overwritten):
+ *   out[0] = sum_i [best_i > thr], out[1] = sum_ij [x_ij > thr], out[2] * 2^-29 + out[3] * 2^-61 = sum x, out[4] * 2^-29 + out[5] * 2^-61 =
+ *   sum best (exact for terms >= 2^-38; smaller ones are cut below 2^-61), out[6] * 2^-29 = sum x[x > thr], out[7] * 2^-29 =
+ *   sum best[best > thr], both exact.
+ *
+ * cft_anchor_kmeans: scipy.cluster.vq.kmeans(obs, k, iter=iters) in float64 (thresh 1e-5), one workgroup, the convergence test on the device.
+ *   obs [n, 2] float64, whitened (device);  idx [iters, k] int (device): the rows each restart starts from (rng.choice(n, k, replace=False));
+ *   book [k, 2] float64: the winning code book, its first info[0] rows;  dist [1] float64: its mean distance;
+ *   info [4] int: surviving codes, winning restart, iterations over all restarts, 1 if a restart hit the iteration bound (100000).
+ * workspace: >= the size cft_anchor_kmeans_workspace_bytes stores in *bytes (host), 256-byte aligned.
+ *
+ * cft_anchor_evolve: the genetic loop (:185-199), one launch per generation, the accept decision on the device.
+ *   v [gen, na, 2] float64 (device): the mutations, drawn by the host;  k [na, 2] float64 (device): the anchors, updated in place;
+ *   per generation kg = max(k * v, 2.0) in float64, fitness of float32(kg): fg = (float)((double)S / (2^29 * n)), S = the integer
+ *   sum of best_i * 2^29 over best_i > thr; accepted when fg > f (float32, strict).
+ *   f [1] float32: the fitness of k (written: first that of the incoming k);  flags [gen] int, fg [gen] float32: the trace.
+ * workspace: >= the size cft_anchor_evolve_workspace_bytes stores in *bytes (host), 256-byte aligned.
+ */
+int cft_anchor_metric(const float* wh, long n, const float* k, int na, float thr, unsigned long long* out, void* stream);
+int cft_anchor_kmeans_workspace_bytes(long n, long* bytes);
+int cft_anchor_kmeans(const double* obs, long n, int k, const int* idx, int iters, void* workspace, long workspace_bytes, double* book,
+                      double* dist, int* info, void* stream);
+int cft_anchor_evolve_workspace_bytes(int gen, long* bytes);
+int cft_anchor_evolve(const float* wh, long n, int na, float thr, const double* v, int gen, double* k, float* f, int* flags, float* fg,
+                      void* workspace, long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
