@@ -118,6 +118,7 @@ def invalidate_packed(root):
     for m in root.modules():
         m.__dict__.pop("_cft_cache", None)
         m.__dict__.pop("_cft_cache_train", None)
+        m.__dict__.pop("_res_chain_cache", None)
         if "_graphs" in m.__dict__:
             m.__dict__["_graphs"].clear()
         m.__dict__.pop("_wlist", None)
@@ -246,23 +247,21 @@ class C3(_Packed):
         c_ = self.cv1.conv.out_channels
         if _act_code(self.cv1.act) != _act_code(self.cv2.act):
             raise NotImplementedError("C3.cv1 and C3.cv2 must share an activation")
-        cat = None
-        if cat is None and isinstance(x, PendingConv) and not self.training:      # the Conv in front of this C3 was left to it: one kernel for both
-            src, conv = resolve(x.x), x.conv
-            pk1 = conv._packed(src.dtype, src.device)
-            if _act_code(conv.act) == ACT_SILU and ops.conv2d_chain_ok(src, pk1, self._packed(src.dtype, src.device)):
-                cat = ops.conv2d_chain(src, pk1, self._packed(src.dtype, src.device), _act_code(self.cv1.act))
-        if cat is not None:
-            pass
-        elif self.training:      # batch statistics are per BatchNorm: cv1 and cv2 run separately into the concat buffer
+        if self.training:        # batch statistics are per BatchNorm: cv1 and cv2 run separately into the concat buffer
             x = resolve(x)
             B, _, H, W = x.shape
             cat = ops.new_nhwc(B, H, W, 2 * c_, x.dtype, x.device)
             self.cv1(x, out=cat[:, :c_])
             self.cv2(x, out=cat[:, c_:])
         else:
-            x = resolve(x)
-            cat = ops.conv2d(x, self._packed(x.dtype, x.device), _act_code(self.cv1.act))     # [B, 2c_, H, W]
+            src = resolve(x.x) if isinstance(x, PendingConv) else resolve(x)
+            pk, act = self._packed(src.dtype, src.device), _act_code(self.cv1.act)
+            pk1 = x.conv._packed(src.dtype, src.device) if isinstance(x, PendingConv) else None
+            if pk1 is not None and _act_code(x.conv.act) == ACT_SILU and ops.conv2d_chain_ok(src, pk1, pk):
+                cat = ops.conv2d_chain(src, pk1, pk, act)       # the Conv in front of this C3 was left to it: one kernel for both
+            else:
+                x = x.conv(src) if pk1 is not None else src
+                cat = ops.conv2d(x, pk, act)     # [B, 2c_, H, W]
         head = cat[:, :c_]
         y = head
         n = len(self.m)
@@ -299,7 +298,9 @@ class C3(_Packed):
         """Every Bottleneck has a shortcut and (cv2[j], cv1[j + 1]) is a pair ``ops.conv2d_chain_res`` takes on tensors shaped like ``y``."""
         if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype in (torch.bfloat16, torch.float16)):
             return False
-        key = (tuple(y.shape), y.dtype, y.device)          # (the decision depends on the pixel grid and the type only: h and y1 are dense tensors of this shape)
+        # the decision depends on the pixel grid and the type (h and y1 are dense tensors of this shape), on the size heuristic that tests
+        # and A/B runs patch, and on the packed weights: invalidate_packed drops the cache with them
+        key = (tuple(y.shape), y.dtype, y.device, ops.CHAIN_RES_MIN_ROWS)
         cache = self.__dict__.setdefault("_res_chain_cache", {})
         if key not in cache:
             if len(cache) > 16:

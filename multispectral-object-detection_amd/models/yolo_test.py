@@ -17,6 +17,7 @@ launches of yolov5l+CFTx3 cost one graph launch.
 """
 import logging
 import math
+from contextlib import nullcontext
 from copy import deepcopy
 from pathlib import Path
 
@@ -25,7 +26,8 @@ import torch.nn as nn
 
 from .. import ops
 from .common import (GPT, NMS, SPP, Add, Add2, Bottleneck, C3, Concat, Conv, Focus, PendingBilinear, PendingConv, Upsample, _Packed, autoShape, resolve,
-                     ACT_NONE, invalidate_packed)
+                     ACT_NONE, invalidate_packed, myTransformerBlock)
+from .layer_graph import LayerGraph, graph_key
 
 logger = logging.getLogger(__name__)
 
@@ -257,108 +259,70 @@ class Model(nn.Module):
             ws = self.__dict__["_wlist"] = list(self.parameters()) + list(self.buffers())
         return hash(tuple(t._version for t in ws))
 
+    # ---- layer graph and plans (models/layer_graph.py) ------------------------------------------------------------------
+    def layer_graph(self):
+        """The ``LayerGraph`` of the current layer list: rebuilt, with every plan, whenever ``self.model`` holds other layers."""
+        g = self.__dict__.get("_layer_graph")
+        if g is None or g.key != graph_key(self.model):
+            g = self.__dict__["_layer_graph"] = LayerGraph(self.model)
+        return g
+
     def stream_lanes(self):
         """Lane (HIP stream) of every layer: the IR backbone - everything reachable from an ``f == -4``
         entry through single-input edges, plus ``Add2(index=1)`` whose base input is the IR feature - is
         lane 1; joins (GPT, Add, Concat, Detect) and the RGB backbone/head are lane 0."""
-        lanes = []
-        for i, m in enumerate(self.model):
-            f = m.f
-            if f == -4:
-                lane = 1
-            elif i == 0:
-                lane = 0
-            elif isinstance(f, int):
-                lane = lanes[i + f] if f < 0 else lanes[f]
-            elif isinstance(m, Add2):
-                j = f[0]
-                lane = lanes[i + j] if j < 0 else lanes[j]
-            else:
-                lane = 0
-            lanes.append(lane)
-        return lanes
+        return list(self.layer_graph().lanes)
 
-    # ---- concat plan: producers write straight into their slice of the consumer's concat buffer --------------
     def concat_plan(self):
         """{producer layer index: (concat layer index, channel offset, channels, total channels)} for every Concat
         source that is a Conv / C3 / Add (they take ``out=``); such a producer's output tensor then IS a channel
         slice of the concat buffer and ``Concat`` skips its copy.  Upsample sources stay deferred copies."""
-        plan = self.__dict__.get("_concat_plan")
-        if plan is not None:
-            return plan
-        layers = list(self.model)
-        memo = {}
+        return self.layer_graph().concat_plan
 
-        def cout(i):
-            if i in memo:
-                return memo[i]
-            m, f = layers[i], layers[i].f
-            src = (lambda j: i + j if j < 0 else j)
-            if isinstance(m, Focus):
-                c = m.conv.conv.out_channels
-            elif type(m) is Conv:
-                c = m.conv.out_channels
-            elif isinstance(m, C3):
-                c = m.cv3.conv.out_channels
-            elif isinstance(m, SPP):
-                c = m.cv2.conv.out_channels
-            elif isinstance(m, Concat):
-                c = sum(cout(src(j)) for j in f)
-            elif isinstance(m, (Add, Add2)):
-                c = cout(src(f[0]))
-            elif isinstance(m, nn.Upsample) and isinstance(f, int):
-                c = cout(src(f))
-            else:
-                c = None                      # GPT tuples, Detect, Sequentials: never a planned source
-            memo[i] = c
-            return c
+    def chain_plan(self):
+        """Indices of the ``Conv`` layers whose output is read by exactly one layer, the ``C3`` right behind them (``f == -1``): yaml
+        rows 1, 3, 6, 8, 13, 15 of the x3 configs (the convs in front of SPP or Concat do not qualify).  Such a conv is handed to its
+        C3 un-run (``PendingConv``); the C3 issues both as one kernel when ``ops.conv2d_chain_ok`` accepts the pair (a conv of 128
+        or 256 output channels: rows 1, 3, 6, 8 of yolov5l), else it runs the conv itself."""
+        return self.layer_graph().chain_plan
 
-        plan = {}
-        try:
-            for i, m in enumerate(layers):
-                if not isinstance(m, Concat) or isinstance(m.f, int):
-                    continue
-                srcs = [i + j if j < 0 else j for j in m.f]
-                chans = [cout(j) for j in srcs]
-                if any(c is None for c in chans):
-                    continue
-                off = 0
-                for j, c in zip(srcs, chans):
-                    if (type(layers[j]) is Conv or isinstance(layers[j], (C3, Add))) and j not in plan and layers[j].f != -4:
-                        plan[j] = (i, off, c, sum(chans))
-                    off += c
-        except (IndexError, KeyError, TypeError, AttributeError):   # foreign module graph (bad `from` index, unknown
-            plan = {}                                               # module type): no plan, Concat copies as before
-        self.__dict__["_concat_plan"] = plan
-        return plan
+    def cft_fusion_plan(self):
+        """{index of the first Add2 behind a GPT block: (GPT index, index of the second Add2, index of the Add that consumes both
+        or None)} - yaml rows 10-12 + 29 (17-19 + 30, 26-28 + 31) of the x3 configs.  The pattern is matched structurally; a config
+        without it (add-fusion, 4-GPT variants with other wiring) simply has no entries."""
+        return self.layer_graph().cft_fusion_plan
 
-    # ---- CFT output fusion: both Add2 layers behind a GPT block and the Add that sums them run as ONE kernel ----------------
-    @property
-    def chain_convs(self):
-        """Run producer / pointwise-consumer layer pairs as one ``cft_conv2d_chain`` kernel where eligible (default): the Conv handed to
-        the C3 behind it (``chain_plan``) and, inside a C3 without shortcuts, ``Bottleneck[j].cv2`` + ``Bottleneck[j+1].cv1``.  ``False``
-        runs every layer as its own launch (A/B; bit-identical results)."""
-        return self.__dict__.get("_chain_convs", True)
-
-    @chain_convs.setter
-    def chain_convs(self, on):
-        self.__dict__["_chain_convs"] = bool(on)
-        for m in self.modules():
-            if isinstance(m, C3):
-                m.chain = bool(on)
-        self.__dict__.get("_graphs", {}).clear()        # a captured graph replays the launches of capture time
+    def prefix_segments(self, max_rows=None):
+        """[(i0, i1)]: maximal runs of layers that depend on ONE image batch only - a ``Focus`` fed by ``x`` (row 0) or ``x2`` (``f == -4``)
+        followed by ``f == -1`` Conv / C3 rows whose outputs have exactly one reader, the next row - cut to ``max_rows`` layers and
+        to end on a C3 (a trailing Conv would be a ``PendingConv`` of a C3 outside the segment).  x3 configs: rows 0-4 and 5-9."""
+        return list(self.layer_graph().prefix_segments(max_rows))
 
     # Executor switches that change WHICH launches a walk issues: a captured graph replays the launches of capture time, so every
-    # setter drops the graphs (ADVICE r4: an A/B flipped after capture() used to compare a path against itself).
-    def _switch(name, default, doc):      # noqa: N805 - class-body helper
+    # setter drops the graphs (ADVICE r4: an A/B flipped after capture() used to compare a path against itself).  ``push``: (sub-module
+    # type, attribute) - an on/off switch whose value the sub-modules of that type carry as well.
+    def _switch(name, default, doc, push=None):      # noqa: N805 - class-body helper
         def get(self):
             return self.__dict__.get("_" + name, default)
 
         def set_(self, v):
+            if push is not None:
+                v = bool(v)
+                for m in self.modules():
+                    if isinstance(m, push[0]):
+                        setattr(m, push[1], v)
             self.__dict__["_" + name] = v
             self.__dict__.get("_graphs", {}).clear()
         return property(get, set_, doc=doc)
 
+    chain_convs = _switch("chain_convs", True,
+                          "Run producer / pointwise-consumer layer pairs as one ``cft_conv2d_chain`` kernel where eligible (default): the Conv handed to "
+                          "the C3 behind it (``chain_plan``) and, inside a C3 without shortcuts, ``Bottleneck[j].cv2`` + ``Bottleneck[j+1].cv1``.  ``False`` "
+                          "runs every layer as its own launch (A/B; bit-identical results).", push=(C3, "chain"))
+    splitk = _switch("splitk", True,
+                     "Run the CFT blocks' out_proj / fc2 GEMMs as split-K launches where ``ops.splitk_choice`` splits them (default; the LayerNorm that "
+                     "follows folds the fp32 partial sums into the residual stream in a fixed order).  ``False``: one launch per GEMM with the residual "
+                     "add in its epilogue (A/B; results differ by fp32 summation order only).", push=(myTransformerBlock, "splitk"))
     fuse_cft_outputs = _switch("fuse_cft_outputs", True, "Run the two Add2 layers behind a GPT block and the Add that sums them as one kernel (cft_fusion_plan).")
     plan_concats = _switch("plan_concats", True, "Let Conv / C3 / Add layers that feed a head Concat write straight into their slice of its buffer (concat_plan).")
     depth_first = _switch("depth_first", None,
@@ -369,37 +333,11 @@ class Model(nn.Module):
                           "bit-identical outputs.  Inference only (BatchNorm batch statistics span the batch).")
     del _switch
 
-    def prefix_segments(self, max_rows=None):
-        """[(i0, i1)]: maximal runs of layers that depend on ONE image batch only - a ``Focus`` fed by ``x`` (row 0) or ``x2`` (``f == -4``)
-        followed by ``f == -1`` Conv / C3 rows whose outputs have exactly one reader, the next row - cut to ``max_rows`` layers and
-        to end on a C3 (a trailing Conv would be a ``PendingConv`` of a C3 outside the segment).  x3 configs: rows 0-4 and 5-9."""
-        layers = list(self.model)
-        readers = {}
-        for j, m in enumerate(layers):
-            if m.f == -4 or j == 0:
-                continue
-            for f in ([m.f] if isinstance(m.f, int) else m.f):
-                readers.setdefault(j - 1 if f == -1 else f % j, set()).add(j)
-        planned = self.concat_plan()
-        segs = []
-        for i0, m in enumerate(layers):
-            if not isinstance(m, Focus) or not (i0 == 0 or m.f == -4):
-                continue
-            i1 = i0
-            while (i1 + 1 < len(layers) and layers[i1 + 1].f == -1 and type(layers[i1 + 1]) in (Conv, C3) and readers.get(i1) == {i1 + 1}
-                   and (i1 + 1) not in planned and (max_rows is None or i1 + 1 - i0 < max_rows)):
-                i1 += 1
-            while i1 > i0 and type(layers[i1]) is not C3:
-                i1 -= 1
-            if i1 > i0:
-                segs.append((i0, i1))
-        return segs
-
-    def _run_segment(self, seg, img, cbufs, chunks):
+    def _run_segment(self, g, seg, img, cbufs, chunks):
         """Layers ``seg = (i0, i1)`` depth-first over ``chunks`` sub-batches of the image batch ``img``; returns the last layer's output
         for the whole batch (each sub-batch's C3 writes its batch slice of it)."""
         i0, i1 = seg
-        layers = self.model
+        layers = g.layers
         B = img.shape[0]
         full = None
         for c in range(chunks):
@@ -408,7 +346,7 @@ class Model(nn.Module):
                 continue
             x = layers[i0](img[b0:b1])
             for i in range(i0 + 1, i1):
-                x = self._run_layer(layers[i], x, None, cbufs)
+                x = self._run_layer(g, layers[i], x, cbufs)
             shape = x.shape                                   # (PendingConv knows its output shape without running)
             if full is None:
                 c2 = layers[i1].cv3.conv.out_channels
@@ -417,74 +355,23 @@ class Model(nn.Module):
             layers[i1](x, out=full[b0:b1])
         return full
 
-    @property
-    def splitk(self):
-        """Run the CFT blocks' out_proj / fc2 GEMMs as split-K launches where ``ops.splitk_choice`` splits them (default; the LayerNorm that
-        follows folds the fp32 partial sums into the residual stream in a fixed order).  ``False``: one launch per GEMM with the residual
-        add in its epilogue (A/B; results differ by fp32 summation order only)."""
-        return self.__dict__.get("_splitk", True)
+    @staticmethod
+    def _concat_slice(g, i, cbufs, B, H, W, dtype, device):
+        """Layer ``i``'s planned channel slice of its consumer's concat buffer (allocated [B, total, H, W] at the first request of a
+        walk), or None: no walk buffers, ``i`` is not planned, or the buffer has another geometry."""
+        tgt = g.concat_plan.get(i) if cbufs is not None else None
+        if tgt is None:
+            return None
+        cidx, off, c, total = tgt
+        buf = cbufs.get(cidx)
+        if buf is None:
+            buf = cbufs[cidx] = ops.new_nhwc(B, H, W, total, dtype, device)
+        return buf[:, off:off + c] if tuple(buf.shape) == (B, total, H, W) else None
 
-    @splitk.setter
-    def splitk(self, on):
-        from .common import myTransformerBlock
-        self.__dict__["_splitk"] = bool(on)
-        for m in self.modules():
-            if isinstance(m, myTransformerBlock):
-                m.splitk = bool(on)
-        self.__dict__.get("_graphs", {}).clear()
-
-    def chain_plan(self):
-        """Indices of the ``Conv`` layers whose output is read by exactly one layer, the ``C3`` right behind them (``f == -1``): yaml
-        rows 1, 3, 6, 8, 13, 15 of the x3 configs (the convs in front of SPP or Concat do not qualify).  Such a conv is handed to its
-        C3 un-run (``PendingConv``); the C3 issues both as one kernel when ``ops.conv2d_chain_ok`` accepts the pair (a conv of 128
-        or 256 output channels: rows 1, 3, 6, 8 of yolov5l), else it runs the conv itself.  Readers are counted from the ``f`` fields, not from
-        ``self.save``: the reference's ``x % i`` book-keeping (models/yolo_test.py:349) files the IR Focus's ``f = -4`` as a reader of
-        row 1, which nothing reads."""
-        plan = self.__dict__.get("_chain_plan")
-        if plan is None:
-            layers = list(self.model)
-            readers = {}
-            for j, m in enumerate(layers):
-                if m.f == -4 or j == 0:
-                    continue
-                for f in ([m.f] if isinstance(m.f, int) else m.f):
-                    readers.setdefault(j - 1 if f == -1 else f % j, set()).add(j)
-            plan = self.__dict__["_chain_plan"] = frozenset(
-                i for i, m in enumerate(layers[:-1])
-                if type(m) is Conv and type(layers[i + 1]) is C3 and layers[i + 1].f == -1 and readers.get(i) == {i + 1})
-        return plan
-
-    def cft_fusion_plan(self):
-        """{index of the first Add2 behind a GPT block: (GPT index, index of the second Add2, index of the Add that consumes both
-        or None)} - yaml rows 10-12 + 29 (17-19 + 30, 26-28 + 31) of the x3 configs.  The pattern is matched structurally; a config
-        without it (add-fusion, 4-GPT variants with other wiring) simply has no entries."""
-        plan = self.__dict__.get("_cft_plan")
-        if plan is not None:
-            return plan
-        layers = list(self.model)
-        src = lambda i, j: i + j if j < 0 else j      # noqa: E731
-        plan = {}
-        for i, m in enumerate(layers):
-            if not isinstance(m, GPT) or not isinstance(m.f, (list, tuple)) or len(m.f) != 2:
-                continue
-            adds = [j for j, a in enumerate(layers) if isinstance(a, Add2) and isinstance(a.f, (list, tuple)) and len(a.f) == 2
-                    and src(j, a.f[1]) == i]
-            if len(adds) != 2 or {layers[adds[0]].index, layers[adds[1]].index} != {0, 1}:
-                continue
-            j1, j2 = adds
-            gin = [src(i, f) for f in m.f]
-            if src(j1, layers[j1].f[0]) != gin[layers[j1].index] or src(j2, layers[j2].f[0]) != gin[layers[j2].index]:
-                continue                               # an Add2 whose base is not the GPT's own input of that stream
-            k = next((kk for kk, a in enumerate(layers) if type(a) is Add and isinstance(a.f, (list, tuple))
-                      and sorted(src(kk, f) for f in a.f) == [j1, j2]), None)
-            plan[j1] = (i, j2, k)
-        self.__dict__["_cft_plan"] = plan
-        return plan
-
-    def _fused_cft_outputs(self, m, x, y, cbufs):
+    def _fused_cft_outputs(self, g, m, x, y, cbufs):
         """Layer ``m`` is the first Add2 of a planned group and its GPT input is still deferred: run the dual de-tokeniser
         (``cft_gpt_upsample_add2``) and return {layer index: output} for the group, else None."""
-        ent = self.cft_fusion_plan().get(m.i)
+        ent = g.cft_fusion_plan.get(m.i)
         if ent is None or not isinstance(x, (list, tuple)) or not isinstance(x[1], (list, tuple)):
             return None
         i, j2, k = ent
@@ -493,41 +380,31 @@ class Model(nn.Module):
             return None
         if not ops.gpt_dual_tokens_ok(p0.tokens):        # the dual kernel is specialised for 2 x 64 fp32 tokens (8 x 8 anchors)
             return None
-        layers = self.model
-        src = lambda a, j: a + j if j < 0 else j      # noqa: E731
+        m2 = g.layers[j2]
         base_m = resolve(x[0])
-        base_o = y[src(j2, layers[j2].f[0])]
+        base_o = y[g.sources[j2][0]]
         if base_o is None or not base_m.is_cuda:
             return None
         base_o = resolve(base_o)
         bases = [None, None]
-        bases[m.index], bases[layers[j2].index] = base_m, base_o
+        bases[m.index], bases[m2.index] = base_m, base_o
         sum_out = None
-        if k is not None and cbufs is not None:       # the Add's planned concat slice (what _run_layer would hand to Add.forward)
-            tgt = self.concat_plan().get(k)
-            if tgt is not None:
-                cidx, off, c, total = tgt
-                B, _, H, W = base_m.shape
-                buf = cbufs.get(cidx)
-                if buf is None:
-                    buf = cbufs[cidx] = ops.new_nhwc(B, H, W, total, base_m.dtype, base_m.device)
-                if tuple(buf.shape) == (B, total, H, W):
-                    sum_out = buf[:, off:off + c]
+        if k is not None:                             # the Add's planned concat slice (what _run_layer would hand to Add.forward)
+            B, _, H, W = base_m.shape
+            sum_out = self._concat_slice(g, k, cbufs, B, H, W, base_m.dtype, base_m.device)
         o0, o1, osum = ops.gpt_upsample_add_dual(p0.tokens, bases[0], bases[1], p0.H, p0.W, p0.dtype, sum_out=sum_out, want_sum=k is not None)
-        outs = {m.i: (o0, o1)[m.index], j2: (o0, o1)[layers[j2].index]}
+        outs = {m.i: (o0, o1)[m.index], j2: (o0, o1)[m2.index]}
         if k is not None:
             outs[k] = osum
         return outs
 
-    def _run_layer(self, m, x, x2, cbufs, chain=True):
-        """``chain=False`` (profiling walks): every layer issues its own launches, so the per-layer table charges a Conv's time to the
-        Conv and not to the C3 that would otherwise run it."""
-        if m.f == -4 or (m.i == 0 and isinstance(m, Focus)):
-            img = x2 if m.f == -4 else x
-            return m(img)
-        tgt = self.concat_plan().get(m.i) if cbufs is not None else None
-        if tgt is not None:
-            cidx, off, c, total = tgt
+    def _run_layer(self, g, m, x, cbufs, chain=True):
+        """One layer on its gathered input ``x`` (an image batch for the rows that consume one).  ``chain=False`` (profiling walks): every
+        layer issues its own launches, so the per-layer table charges a Conv's time to the Conv and not to the C3 that would otherwise
+        run it."""
+        if g.image[m.i] == 1 or (m.i == 0 and isinstance(m, Focus)):
+            return m(x)
+        if cbufs is not None and m.i in g.concat_plan:
             t = x[0] if isinstance(x, (list, tuple)) else x
             shape = t.shape if isinstance(t, PendingConv) else None     # (stays un-run: only its geometry is needed here)
             t = t.x if isinstance(t, PendingConv) else resolve(t)
@@ -535,14 +412,12 @@ class Model(nn.Module):
                 B, _, H, W = shape or t.shape
                 if type(m) is Conv:
                     H, W = ops.conv_out_size(H, W, m.conv.kernel_size[0], m.conv.stride[0])
-                buf = cbufs.get(cidx)
-                if buf is None:
-                    buf = cbufs[cidx] = ops.new_nhwc(B, H, W, total, t.dtype, t.device)
-                if tuple(buf.shape) == (B, total, H, W):
-                    return m(x, out=buf[:, off:off + c])
+                out = self._concat_slice(g, m.i, cbufs, B, H, W, t.dtype, t.device)
+                if out is not None:
+                    return m(x, out=out)
         if cbufs is not None and isinstance(m, Concat) and m.i in cbufs:
             return m(x, out=cbufs[m.i])
-        if (chain and cbufs is not None and not self.training and m.i in self.chain_plan() and self.chain_convs
+        if (chain and cbufs is not None and not self.training and m.i in g.chain_plan and self.chain_convs
                 and isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16)):
             return PendingConv(m, x)                 # left to the C3 behind it (one kernel for the conv and the C3's cv1|cv2)
         return m(x)
@@ -555,99 +430,85 @@ class Model(nn.Module):
         The two backbones are independent between fusion points, so with ``overlap_streams`` they are
         enqueued on two HIP streams (fork/join by stream waits; inside a HIP-graph capture this becomes
         two parallel branches of the graph).  Every tensor that crosses lanes is a saved layer output
-        and stays referenced in ``y`` until the walk ends, so the caching allocator cannot recycle it
-        under a kernel of the other stream."""
-        layers = list(self.model)
+        and stays referenced (``keep``) until the lanes have joined, so the caching allocator cannot recycle it
+        under a kernel of the other stream.  A one-lane walk (``lanes is None``) has no side stream, no waits and keeps nothing."""
+        g = self.layer_graph()
+        layers = g.layers
         if until_detect and layers and type(layers[-1]) is NMS:
             layers = layers[:-1]
-        lanes = self.stream_lanes() if (self.overlap_streams and x.is_cuda and not profile) else None
+        lanes = g.lanes if (self.overlap_streams and x.is_cuda and not profile) else None
+        if lanes is not None and 1 not in lanes:
+            lanes = None
         fused = {}                                                    # outputs of a CFT output group still to be handed to their layers
         fuse_cft = x.is_cuda and self.fuse_cft_outputs and not profile      # profile: one launch group per layer (the reference's per-layer table)
         cbufs = {} if (x.is_cuda and self.plan_concats) else None   # planned concat buffers of this walk
         # depth-first prefix (Model.depth_first): {first row: (i0, i1)} and the rows a segment covers
         seg_at, seg_rows, df = {}, set(), self.depth_first
         if df and x.is_cuda and not self.training and not profile and cbufs is not None and x.shape[0] >= 2 * int(df[0]) > 0:
-            for sg in self.prefix_segments(df[1] if len(df) > 1 else None):
+            for sg in g.prefix_segments(df[1] if len(df) > 1 else None):
                 seg_at[sg[0]] = sg
                 seg_rows.update(range(sg[0], sg[1] + 1))
-        if lanes is None or 1 not in lanes:
-            y, marks = [], []
-            if profile:     # reference :252-260,270-271: per-layer time / GFLOPS / params / type.  One stream, HIP events around
-                flog, prev_log = [], ops._launch_log         # every layer, GFLOPS from the algorithmic FLOPs of its GEMM launches
-                ops.set_launch_log(flog)
-            try:
-                for m in layers:
-                    if m.i in seg_rows:                       # depth-first prefix: the whole segment runs at its first row
-                        if m.i in seg_at:
-                            x = self._run_segment(seg_at[m.i], x2 if m.f == -4 else x, cbufs, int(df[0]))
-                            seg_end = seg_at[m.i][1]
-                        y.append(x if (m.i == seg_end and m.i in self.save) else None)
-                        continue
-                    if m.f != -1 and m.f != -4:
-                        x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
-                    if profile:
-                        e0, e1, n0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), len(flog)
-                        e0.record()
-                    if m.i in fused:
-                        x = fused.pop(m.i)
+        on_lane = lambda i: nullcontext()      # noqa: E731
+        if lanes is not None:
+            main = torch.cuda.current_stream(x.device)
+            side = self.__dict__.get("_side_stream")
+            if side is None or side.device != x.device:
+                side = self.__dict__["_side_stream"] = torch.cuda.Stream(device=x.device)
+            streams, keep = (main, side), []             # keep every output alive until both lanes have joined
+            on_lane = lambda i: torch.cuda.stream(streams[lanes[i]])      # noqa: E731
+            side.wait_stream(main)                       # fork: the side lane starts after everything queued so far
+        if profile:     # reference :252-260,270-271: per-layer time / GFLOPS / params / type.  One stream, HIP events around
+            flog, prev_log, marks = [], ops._launch_log, []      # every layer, GFLOPS from the algorithmic FLOPs of its GEMM launches
+            ops.set_launch_log(flog)
+        y, seg_end = [], None
+        try:
+            for i, m in enumerate(layers):
+                if i in seg_rows:                             # depth-first prefix: the whole segment runs at its first row, on its lane
+                    if i in seg_at:
+                        with on_lane(i):
+                            x = self._run_segment(g, seg_at[i], x2 if g.image[i] else x, cbufs, int(df[0]))
+                        seg_end = seg_at[i][1]
+                        if lanes is not None:
+                            keep.append(x)
+                    y.append(x if (i == seg_end and i in self.save) else None)
+                    continue
+                if lanes is not None and any(lanes[j] != lanes[i] for j in g.sources[i]):
+                    streams[lanes[i]].wait_stream(streams[1 - lanes[i]])
+                if g.image[i] is None:
+                    x = g.inputs(i, x, y)
+                elif g.image[i]:
+                    x = x2                           # (row 0: x is still the RGB image; no other reference to it is kept)
+                if profile:
+                    e0, e1, n0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), len(flog)
+                    e0.record()
+                with on_lane(i):
+                    if i in fused:
+                        x = fused.pop(i)         # produced by the group's kernel, maybe on the other lane: the cross-lane wait above orders it
                     else:
-                        grp = self._fused_cft_outputs(m, x, y, cbufs) if fuse_cft else None
+                        grp = self._fused_cft_outputs(g, m, x, y, cbufs) if fuse_cft else None
                         if grp is not None:
-                            x = grp.pop(m.i)
+                            x = grp.pop(i)
                             fused.update(grp)
                         else:
-                            x = self._run_layer(m, x, x2, cbufs, chain=not profile)
-                    if profile:
-                        e1.record()
-                        marks.append((m, e0, e1, sum(rec[1] for rec in flog[n0:])))
-                    y.append(x if m.i in self.save else None)
-            finally:
+                            x = self._run_layer(g, m, x, cbufs, chain=not profile)
                 if profile:
-                    ops.set_launch_log(prev_log)
-            if profile:
-                torch.cuda.synchronize(x[0].device if isinstance(x, (tuple, list)) else x.device)
-                self.profile_ms = [(m.i, m.type, e0.elapsed_time(e1), fl / 1e9, m.np) for m, e0, e1, fl in marks]
-                logger.info(f"{'time (ms)':>10s} {'GFLOPS':>10s} {'params':>10s}  {'module'}")
-                for i, t, ms, gf, np_ in self.profile_ms:
-                    logger.info(f"{ms:10.2f} {gf:10.2f} {np_:10.0f}  {t}")
-                logger.info('%.1fms total' % sum(r[2] for r in self.profile_ms))
-            return x
-        main = torch.cuda.current_stream(x.device)
-        side = self.__dict__.get("_side_stream")
-        if side is None or side.device != x.device:
-            side = self.__dict__["_side_stream"] = torch.cuda.Stream(device=x.device)
-        streams = (main, side)
-        side.wait_stream(main)                       # fork: the side lane starts after everything queued so far
-        y, keep = [], []
-        for i, m in enumerate(layers):
-            lane = lanes[i]
-            f = m.f
-            if m.i in seg_rows:                               # depth-first prefix: the whole segment runs at its first row, on its lane
-                if m.i in seg_at:
-                    with torch.cuda.stream(streams[lane]):
-                        x = self._run_segment(seg_at[m.i], x2 if f == -4 else x, cbufs, int(df[0]))
-                    seg_end = seg_at[m.i][1]
+                    e1.record()
+                    marks.append((m, e0, e1, sum(rec[1] for rec in flog[n0:])))
+                if lanes is not None:
                     keep.append(x)
-                y.append(x if (m.i == seg_end and m.i in self.save) else None)
-                continue
-            srcs = [] if (f == -4 or i == 0) else ([i - 1] if f == -1 else ([f % i] if isinstance(f, int) else [(i - 1 if j == -1 else j % i) for j in f]))
-            if any(lanes[j] != lane for j in srcs):
-                streams[lane].wait_stream(streams[1 - lane])
-            if f != -1 and f != -4:
-                x = y[f] if isinstance(f, int) else [x if j == -1 else y[j] for j in f]
-            with torch.cuda.stream(streams[lane]):
-                if m.i in fused:
-                    x = fused.pop(m.i)       # produced by the group's kernel on the other lane: the cross-lane wait above orders it
-                else:
-                    grp = self._fused_cft_outputs(m, x, y, cbufs) if fuse_cft else None
-                    if grp is not None:
-                        x = grp.pop(m.i)
-                        fused.update(grp)
-                    else:
-                        x = self._run_layer(m, x, x2, cbufs)
-            keep.append(x)                           # keep every output alive until both lanes have joined
-            y.append(x if m.i in self.save else None)
-        main.wait_stream(side)                       # join
+                y.append(x if i in self.save else None)
+        finally:
+            if profile:
+                ops.set_launch_log(prev_log)
+        if lanes is not None:
+            main.wait_stream(side)                       # join
+        if profile:
+            torch.cuda.synchronize(x[0].device if isinstance(x, (tuple, list)) else x.device)
+            self.profile_ms = [(m.i, m.type, e0.elapsed_time(e1), fl / 1e9, m.np) for m, e0, e1, fl in marks]
+            logger.info(f"{'time (ms)':>10s} {'GFLOPS':>10s} {'params':>10s}  {'module'}")
+            for i, t, ms, gf, np_ in self.profile_ms:
+                logger.info(f"{ms:10.2f} {gf:10.2f} {np_:10.0f}  {t}")
+            logger.info('%.1fms total' % sum(r[2] for r in self.profile_ms))
         return x
 
     def _initialize_biases(self, cf=None):  # reference :274-282
@@ -679,9 +540,6 @@ class Model(nn.Module):
         elif not mode and present:
             logger.info("Removing NMS... ")
             self.model = self.model[:-1]
-        self.__dict__.pop("_concat_plan", None)
-        self.__dict__.pop("_cft_plan", None)
-        self.__dict__.pop("_chain_plan", None)
         self._graphs.clear()
         return self
 

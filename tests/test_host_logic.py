@@ -479,6 +479,35 @@ def test_prefix_segments_and_executor_switches():
         assert getattr(m, name) == value and not m._graphs, name
 
 
+def test_executor_plans_reproduce_the_recorded_ones_and_follow_the_layer_list():
+    """tests/golden/exec/plans.json (make_exec_golden.py): lanes, concat plan, chain plan, CFT fusion plan and prefix segments of the four
+    graph structures, plain and after ``nms()``, are reproduced exactly; the cached layer graph is rebuilt whenever ``model.model`` holds
+    other layers - ``nms()``, ``nms(False)``, a slice - without anybody naming a cache."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_exec_golden as recipe
+    with open(os.path.join(ROOT, "tests", "golden", "exec", "plans.json")) as fh:
+        want = json.load(fh)
+    assert sorted(want) == sorted(recipe.STRUCTURES)
+    assert want[recipe.X4]["plain"]["cft"]["7"] == [6, 8, None]          # the 4-GPT layout's P2 group has no Add
+    for name in recipe.STRUCTURES:
+        m = Model(configs.named_config(name))
+        plain = json.loads(json.dumps(recipe.plans(m)))
+        assert plain == want[name]["plain"], name
+        g0, n = m.layer_graph(), len(m.model)
+        assert m.layer_graph() is g0                                     # cached while the layer list stands
+        m.nms()
+        assert m.layer_graph() is not g0 and len(m.stream_lanes()) == n + 1
+        assert json.loads(json.dumps(recipe.plans(m))) == want[name]["nms"], name
+        m.nms(False)
+        assert len(m.stream_lanes()) == n and json.loads(json.dumps(recipe.plans(m))) == plain
+        m.model = m.model[:n - 1]                                        # drop Detect: the plans describe the 'n - 1' layers that are left
+        assert len(m.layer_graph().layers) == n - 1 and len(m.stream_lanes()) == n - 1
+        assert m.concat_plan() == {int(k): tuple(v) for k, v in want[name]["plain"]["concat"].items()}
+        assert m.chain_plan() == frozenset(want[name]["plain"]["chain"])
+
+
 def test_splitk_choice_rule():
     """ops.splitk_choice (host decision, measured in profiles/r05_splitk_ab.md): split only GEMMs on the uniform K walk whose 256 x 256 tiles
     leave >= 3/4 of the chip idle, only up to SPLITK_MAX_ROWS token rows, to the smallest split that yields 128 workgroups with >= 4 K
