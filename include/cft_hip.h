@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bump with every change of a prototype below (history: csrc/runtime.hip).  The Python binding reads this line, the enums and
  * every prototype from this file: it is the only description of the ABI. */
-#define CFT_ABI_VERSION 16
+#define CFT_ABI_VERSION 17
 
 enum { CFT_BF16 = 0, CFT_F32 = 1, CFT_F16 = 2 };
 enum { CFT_ACT_NONE = 0, CFT_ACT_SILU = 1, CFT_ACT_GELU = 2 };
@@ -196,6 +196,37 @@ int cft_to_nhwc(const void* in, int in_dtype, long stride_b, long stride_c, long
 int cft_letterbox_u8(const unsigned char* src, int src_h, int src_w, long src_row_stride,
                      unsigned char* dst, int dst_h, int dst_w, long dst_stride_y, long dst_stride_x, long dst_stride_c, int flip_channels,
                      int resized_h, int resized_w, int top, int left, int color0, int color1, int color2, void* stream);
+
+/*
+ * One launch assembles the whole uint8 [B, 6, dst_h, dst_w] batch of a non-augmented RGB + IR dataloader (RGB in planes 0-2, IR in
+ * planes 3-5): per pair everything between cv2.imread and torch.from_numpy(img_all) of LoadMultiModalImagesAndLabels.__getitem__
+ * (utils/datasets.py:1201-1207, :1274-1279) - the load_image_rgb_ir resize (:1361-1367), the grey letterbox border (auto=False,
+ * scaleup=False: no second resize, the caller checks that) and HWC -> CHW.  The table has one cft_pair_desc_t row per pair:
+ *   mode CFT_PAIR_COPY   (r == 1): h == h0, w == w0;
+ *        CFT_PAIR_LINEAR (r > 1) : cv2 INTER_LINEAR for 8-bit, the arithmetic of cft_letterbox_u8, bit for bit;
+ *        CFT_PAIR_AREA   (r < 1) : cv2 INTER_AREA for 8-bit: output (dy, dx) = the box average of the source over
+ *                                  [dx*w0/w, (dx+1)*w0/w) x [dy*h0/h, (dy+1)*h0/h), edge cells weighted by their covered fraction
+ *                                  as computeResizeAreaTab does, fp32 accumulation (columns of a row, then the rows), rounded to
+ *                                  nearest; when w0 % w == 0 and h0 % h == 0 the exact integer block mean, halves rounded up.
+ *   flip: 0 = the source channel order is the plane order (RGB sources, e.g. PIL), 1 = reversed (BGR sources, as cv2.imread gives).
+ * desc_dev is the table in device memory (what the kernel reads), desc_host the same bytes in host memory (what the guards read:
+ * every row is checked before the launch - sizes, fit, strides, mode, a reduction of at most 4x per axis, what the LDS span of a tile admits - and nothing is launched
+ * on CFT_EINVAL).  dst % 4 == 0 and dst_w % 4 == 0 (rows are written as dwords); color = the border value of all three channels.
+ * The sources may differ in size, mode and row stride within one launch.
+ */
+enum { CFT_PAIR_COPY = 0, CFT_PAIR_LINEAR = 1, CFT_PAIR_AREA = 2 };
+#define CFT_PAIR_DESC_BYTES 64
+#define CFT_PAIR_MAX_REDUCTION 4   /* CFT_PAIR_AREA: h0 <= 4 h and w0 <= 4 w (what one tile's source span in LDS admits) */
+typedef struct {
+  const unsigned char* src_rgb;   /* HWC uint8, pixels contiguous */
+  const unsigned char* src_ir;
+  long stride_rgb, stride_ir;     /* source row strides in bytes, >= 3 * w0 */
+  int h0, w0;                     /* source size */
+  int h, w;                       /* resized size */
+  int top, left;                  /* where the resized image sits in the dst_h x dst_w letterbox */
+  int mode, flip;
+} cft_pair_desc_t;
+int cft_pair_batch_u8(const void* desc_dev, const void* desc_host, int B, unsigned char* dst, int dst_h, int dst_w, int color, void* stream);
 
 /* Elementwise out = a + b over M pixels x C channels (Add / Add2, models/common.py:228-243). */
 int cft_add(const void* a, int lda, int aoff, const void* b, int ldb, int boff,

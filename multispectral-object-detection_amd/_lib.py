@@ -16,10 +16,10 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: experiments with an alternative build, e.g. the probe library)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "confusion.hip", "loss.hip", "autoanchor.hip")
+SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip")
 
 HEADER = os.path.join(_HERE, "..", "include", "cft_hip.h")
-HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "conv_gemm_asm.inc")
+HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "resize_common.h", "conv_gemm_asm.inc")
 
 _SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong}
 _RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}

@@ -57,13 +57,16 @@ def _apriori_rows(targets, B, no, H, W):
 
 
 def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None, confusion=False,
-             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None):
+             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None):
     """batches: an iterable of ``(img6_uint8 [B, 6, H, W], targets [nt, 6], paths, shapes)`` as test.py's dataloader yields.
     Returns test.py's ``((mp, mr, map50, map75, map), maps)``; with ``compute_loss``, test.py's
     ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches.
 
     With any of ``confusion``, ``save_txt``, ``save_hybrid``, ``save_json`` (module docstring) a third element follows:
-    ``{"confusion_matrix": (nc+1, nc+1) float64 numpy array or None, "jdict": list of entries or None}``."""
+    ``{"confusion_matrix": (nc+1, nc+1) float64 numpy array or None, "jdict": list of entries or None}``.
+
+    ``details``: a dict that receives ``"result"``, the ``EvalResult`` behind the returned tuple (per-class p / r / ap, nt, seen - what
+    test.py's table prints, tools/val.py); the return value does not change."""
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model must be on the GPU (this package has no CPU path)")
@@ -103,6 +106,8 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
                     jdict.extend(json_entry(stem, r[5], r[12:16], r[4]) for r in rows)
         nb += 1
     res = ev.compute()
+    if details is not None:
+        details["result"] = res
     results, maps = res.as_test_tuple()
     if compute_loss is not None:
         losses = (loss.cpu() / nb).tolist() if nb else [0.0, 0.0, 0.0]          # test.py:295

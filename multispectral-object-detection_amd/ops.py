@@ -705,6 +705,23 @@ def detect_decode(logits, raw, pred, anchors_px, na, no, stride, row0):
     _lib.check(st, "cft_detect_decode")
 
 
+def pair_batch_u8(desc_dev, desc_host, out, color=114):
+    """One launch assembles the uint8 [B, 6, H, W] RGB + IR batch ``out`` from a table of cft_pair_desc_t rows (cft_pair_batch_u8):
+    ``desc_dev`` [B, 64] uint8 on the device is what the kernel reads, ``desc_host`` the same bytes on the host is what the guards read."""
+    _require_cuda(out, "pair_batch_u8")
+    _require_cuda(desc_dev, "pair_batch_u8")
+    B = out.shape[0]
+    if out.dtype != torch.uint8 or out.dim() != 4 or out.shape[1] != 6 or not out.is_contiguous():
+        raise ValueError(f"pair_batch_u8: out must be a contiguous uint8 [B, 6, H, W] tensor, got {out.dtype} {tuple(out.shape)}")
+    for t, what in ((desc_dev, "desc_dev"), (desc_host, "desc_host")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (B, _lib._consts["CFT_PAIR_DESC_BYTES"]) or not t.is_contiguous():
+            raise ValueError(f"pair_batch_u8: {what} must be a contiguous uint8 [{B}, {_lib._consts['CFT_PAIR_DESC_BYTES']}] tensor")
+    if desc_host.is_cuda:
+        raise ValueError("pair_batch_u8: desc_host must be a host tensor")
+    st = _lib.load().cft_pair_batch_u8(desc_dev.data_ptr(), desc_host.data_ptr(), B, out.data_ptr(), out.shape[2], out.shape[3], int(color), _stream())
+    _lib.check(st, "cft_pair_batch_u8")
+    return out
+
 
 # ------------------------------------------------------------------------------ training-mode forward
 _dropout_state = {"seed": 0x5EED, "calls": 0}

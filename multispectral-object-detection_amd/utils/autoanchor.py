@@ -167,7 +167,9 @@ def _shapes_labels(path):
 
 
 def kmean_anchors(path, n=9, img_size=640, thr=4.0, gen=1000, verbose=True):
-    """k-means anchors evolved by the genetic loop (reference utils/autoanchor.py:103-201).  Returns ``k`` [n, 2] float64, sorted by area."""
+    """k-means anchors evolved by the genetic loop (reference utils/autoanchor.py:103-201).  Returns ``k`` [n, 2] float64, sorted by area.
+    ``path``: a dataset object with ``.shapes`` and ``.labels`` - ``utils.datasets.LoadMultiModalImagesAndLabels(path_rgb, path_ir, ...)`` is
+    the way to run it on a dataset on disk - or a ``(shapes, labels)`` pair; a ``*.yaml`` path raises."""
     thr = 1. / thr
     dataset_shapes, labels = _shapes_labels(path)
     dev = _device_of()

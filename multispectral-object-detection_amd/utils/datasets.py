@@ -2,12 +2,15 @@
 ``letterbox`` of the reference's ``utils/datasets.py:1698-1728`` - resize to a stride-friendly shape keeping the
 aspect ratio, pad with grey - on the device, one kernel per image (``cft_letterbox_u8``), and the pair packer that
 builds the uint8 ``[B,6,H,W]`` batch the model consumes (``utils/datasets.py:1274-1281``: BGR->RGB, HWC->CHW)."""
+import glob
+import os
+from pathlib import Path
+
 import numpy as np
 import torch
 
 from .. import _lib
 from ..ops import _require_cuda, _stream
-
 
 def letterbox_geometry(shape, new_shape=(640, 640), auto=True, scaleFill=False, scaleup=True, stride=32):
     """The arithmetic of reference utils/datasets.py:1700-1726, verbatim in meaning: returns
@@ -70,3 +73,499 @@ def letterbox_pair(img_rgb, img_ir, new_shape=640, stride=32, auto=False, scaleu
     _, ratio, pad = letterbox(img_rgb, new_shape, auto=auto, scaleup=scaleup, stride=stride, out=out[:3])
     letterbox(img_ir, new_shape, auto=auto, scaleup=scaleup, stride=stride, out=out[3:])
     return out, ratio, pad
+
+
+# ------------------------------------------------------------------------------ paired RGB + IR dataset, validation form
+# The non-augmented (validation / rect) form of the reference's LoadMultiModalImagesAndLabels and create_dataloader_rgb_ir
+# (utils/datasets.py:820-1288, :223-257).  The host keeps the reference's bookkeeping - file lists, label checks, the rect sort and
+# batch shapes, targets and shapes - and decodes the files; everything between the decoded originals and the uint8 [B,6,H,W] batch
+# is ONE launch of cft_pair_batch_u8 per batch (csrc/dataset.hip).
+img_formats = ['bmp', 'jpg', 'jpeg', 'png', 'tif', 'tiff', 'dng', 'webp', 'mpo']  # acceptable image suffixes (reference :33)
+PAIR_COPY, PAIR_LINEAR, PAIR_AREA = (_lib._consts[k] for k in ("CFT_PAIR_COPY", "CFT_PAIR_LINEAR", "CFT_PAIR_AREA"))
+PAIR_MODE_NAMES = {PAIR_COPY: "copy", PAIR_LINEAR: "linear", PAIR_AREA: "area"}
+# one row of the table cft_pair_batch_u8 reads: cft_pair_desc_t of include/cft_hip.h
+PAIR_DESC = np.dtype([("src_rgb", "<u8"), ("src_ir", "<u8"), ("stride_rgb", "<i8"), ("stride_ir", "<i8"), ("h0", "<i4"), ("w0", "<i4"),
+                      ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("mode", "<i4"), ("flip", "<i4")])
+assert PAIR_DESC.itemsize == _lib._consts["CFT_PAIR_DESC_BYTES"]
+PAIR_MAX_REDUCTION = _lib._consts["CFT_PAIR_MAX_REDUCTION"]
+MAX_DECODE_THREADS = 16
+
+
+class LetterboxResizes(AssertionError):
+    """Raised where a batch's table is built if the letterbox itself would resize a pair: cft_pair_batch_u8 has one resize stage,
+    the loader then assembles that batch pair by pair with ``letterbox_pair``."""
+
+
+def img2label_paths(img_paths):
+    """Label paths as a function of image paths (reference utils/datasets.py:518-521): /images/ -> /labels/, suffix -> txt."""
+    sa, sb = os.sep + 'images' + os.sep, os.sep + 'labels' + os.sep  # /images/, /labels/ substrings
+    return ['txt'.join(x.replace(sa, sb, 1).rsplit(x.split('.')[-1], 1)) for x in img_paths]
+
+
+def xywhn2xyxy(x, w=640, h=640, padw=0, padh=0):
+    """nx4 boxes from normalised [x, y, w, h] to pixel [x1, y1, x2, y2] (reference utils/general.py:309-316)."""
+    y = x.clone() if isinstance(x, torch.Tensor) else np.copy(x)
+    y[:, 0] = w * (x[:, 0] - x[:, 2] / 2) + padw  # top left x
+    y[:, 1] = h * (x[:, 1] - x[:, 3] / 2) + padh  # top left y
+    y[:, 2] = w * (x[:, 0] + x[:, 2] / 2) + padw  # bottom right x
+    y[:, 3] = h * (x[:, 1] + x[:, 3] / 2) + padh  # bottom right y
+    return y
+
+
+def xyxy2xywh(x):
+    """nx4 boxes from [x1, y1, x2, y2] to [x, y, w, h], tensors and numpy arrays alike (reference utils/general.py:289-296)."""
+    y = x.clone() if isinstance(x, torch.Tensor) else np.copy(x)
+    y[:, 0] = (x[:, 0] + x[:, 2]) / 2  # x center
+    y[:, 1] = (x[:, 1] + x[:, 3]) / 2  # y center
+    y[:, 2] = x[:, 2] - x[:, 0]  # width
+    y[:, 3] = x[:, 3] - x[:, 1]  # height
+    return y
+
+
+def _exif_size(img):
+    """Exif-corrected PIL size (reference utils/datasets.py:89-101)."""
+    from PIL import ExifTags
+    orientation = next((k for k, v in ExifTags.TAGS.items() if v == 'Orientation'), None)
+    s = img.size  # (width, height)
+    try:
+        rotation = dict(img._getexif().items())[orientation]
+        if rotation in (6, 8):  # rotation 270 / 90
+            s = (s[1], s[0])
+    except Exception:
+        pass
+    return s
+
+
+def _list_images(path, prefix=''):
+    """Image files of a directory (recursive), a *.txt list, or a list of those (reference utils/datasets.py:859-895)."""
+    f = []
+    for p in path if isinstance(path, list) else [path]:
+        p = Path(p)  # os-agnostic
+        if p.is_dir():  # dir
+            f += glob.glob(str(p / '**' / '*.*'), recursive=True)
+        elif p.is_file():  # file
+            with open(p, 'r') as t:
+                t = t.read().strip().splitlines()
+                parent = str(p.parent) + os.sep
+                f += [x.replace('./', parent) if x.startswith('./') else x for x in t]  # local to global path
+        else:
+            raise Exception(f'{prefix}{p} does not exist')
+    return sorted([x.replace('/', os.sep) for x in f if x.split('.')[-1].lower() in img_formats])
+
+
+def verify_image_label(im_file, lb_file):
+    """The per-image checks of the reference's ``cache_labels`` (utils/datasets.py:1097-1127): returns ``(labels [n, 5] float32,
+    shape (w, h), state)`` with state 'found' / 'empty' / 'missing'; raises (AssertionError, OSError, ValueError) where the reference
+    counts the image as corrupted and ignores it."""
+    from PIL import Image
+    im = Image.open(im_file)
+    im.verify()  # PIL verify
+    shape = _exif_size(im)  # image size
+    assert (shape[0] > 9) & (shape[1] > 9), f'image size {shape} <10 pixels'
+    assert im.format.lower() in img_formats, f'invalid image format {im.format}'
+    if not os.path.isfile(lb_file):
+        return np.zeros((0, 5), dtype=np.float32), shape, 'missing'
+    with open(lb_file, 'r') as f:
+        l = [x.split() for x in f.read().strip().splitlines()]
+    if any([len(x) > 8 for x in l]):
+        raise ValueError('segment labels are not supported (only the box form: class x y w h)')
+    l = np.array(l, dtype=np.float32)
+    if not len(l):
+        return np.zeros((0, 5), dtype=np.float32), shape, 'empty'
+    assert l.shape[1] == 5, 'labels require 5 columns each'
+    assert (l >= 0).all(), 'negative labels'
+    assert (l[:, 1:] <= 1).all(), 'non-normalized or out of bounds coordinate labels'
+    assert np.unique(l, axis=0).shape[0] == l.shape[0], 'duplicate labels'
+    return l, shape, 'found'
+
+
+def decode_image(path):
+    """One image file as an HWC uint8 array in RGB order (PIL; the reference's cv2.imread gives the same pixels in BGR order)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert('RGB'))
+
+
+class LoadMultiModalImagesAndLabels:  # for testing
+    """The reference's paired RGB + IR dataset (utils/datasets.py:820-1288), same constructor, in its non-augmented form:
+    ``augment=True`` (mosaic, HSV, flips, perspective) raises NotImplementedError.  Differences that are deliberate:
+
+    * labels are held in memory, no ``.cache`` file is written beside the data;
+    * the reference sorts the RGB and the IR list independently (one order for aligned pairs): here the RGB order is applied to
+      both lists, a pair that the reference would ignore as corrupted in either list is dropped as a pair, and a pair whose two
+      images differ in size raises ValueError;
+    * ``cache_images`` (True or 'device') keeps the decoded originals as uint8 CUDA tensors after the first pass of the loader.
+
+    ``shapes`` / ``labels`` / ``img_files_rgb`` / ``img_files_ir`` / ``n`` / ``batch_rgb`` / ``batch_shapes_rgb`` / ``indices_rgb``
+    are the reference's attributes, so the object can be handed to ``check_anchors_rgb_ir`` and ``kmean_anchors``."""
+
+    def __init__(self, path_rgb, path_ir, img_size=640, batch_size=16, augment=False, hyp=None, rect=False, image_weights=False,
+                 cache_images=False, single_cls=False, stride=32, pad=0.0, prefix=''):
+        if augment:
+            raise NotImplementedError("LoadMultiModalImagesAndLabels: augment=True (mosaic, HSV, flips, perspective) is not implemented; "
+                                      "this package builds the non-augmented validation / rect form only")
+        if cache_images not in (False, None, True, 'device'):
+            raise ValueError(f"cache_images must be False, True or 'device', got {cache_images!r}")
+        self.img_size = img_size
+        self.augment = augment
+        self.hyp = hyp
+        self.image_weights = image_weights
+        self.rect = False if image_weights else rect
+        self.mosaic = False
+        self.stride = stride
+        self.path_rgb = path_rgb
+        self.path_ir = path_ir
+        self.pad = pad
+        self.cache_images = bool(cache_images)
+
+        try:
+            files_rgb, files_ir = _list_images(path_rgb, prefix), _list_images(path_ir, prefix)
+            assert files_rgb and files_ir, f'{prefix}No images found'
+        except Exception as e:
+            raise Exception(f'{prefix}Error loading data from {path_rgb, path_ir}: {e}')
+        if len(files_rgb) != len(files_ir):
+            raise ValueError(f'{prefix}{len(files_rgb)} RGB images but {len(files_ir)} IR images: the two lists do not pair up')
+
+        # labels and shapes (cache_labels, :1089-1144), in memory
+        self.img_files_rgb, self.img_files_ir, labels, shapes = [], [], [], []
+        nf = nm = ne = nc = 0  # number found, missing, empty, corrupted
+        for f_rgb, f_ir, l_rgb, l_ir in zip(files_rgb, files_ir, img2label_paths(files_rgb), img2label_paths(files_ir)):
+            try:
+                l, shape, state = verify_image_label(f_rgb, l_rgb)
+                _, shape_ir, _ = verify_image_label(f_ir, l_ir)
+            except (AssertionError, OSError, ValueError, SyntaxError) as e:
+                nc += 1
+                print(f'{prefix}WARNING: Ignoring corrupted image and/or label {f_rgb}: {e}')
+                continue
+            if tuple(shape) != tuple(shape_ir):
+                raise ValueError(f'{prefix}unaligned pair: {f_rgb} is {shape[0]}x{shape[1]} but {f_ir} is {shape_ir[0]}x{shape_ir[1]}')
+            nf, nm, ne = nf + (state == 'found'), nm + (state == 'missing'), ne + (state == 'empty')
+            self.img_files_rgb.append(f_rgb)
+            self.img_files_ir.append(f_ir)
+            labels.append(l)
+            shapes.append(shape)
+        self.scan_results = nf, nm, ne, nc, len(files_rgb)
+        if not shapes:
+            raise Exception(f'{prefix}No usable image pairs in {path_rgb, path_ir}')
+        self.labels_rgb = labels
+        self.shapes_rgb = np.array(shapes, dtype=np.float64)
+        self.label_files_rgb = img2label_paths(self.img_files_rgb)
+        self.label_files_ir = img2label_paths(self.img_files_ir)
+        if single_cls:
+            for x in self.labels_rgb:
+                x[:, 0] = 0
+
+        n = len(shapes)  # number of images
+        bi = np.floor(np.arange(n) / batch_size).astype(int)  # batch index
+        nb = bi[-1] + 1  # number of batches
+        self.batch_rgb = bi  # batch index of image
+        self.n = self.n_rgb = n
+        self.indices_rgb = range(n)
+
+        # Rectangular Training (:1009-1032)
+        if self.rect:
+            s = self.shapes_rgb  # wh
+            ar = s[:, 1] / s[:, 0]  # aspect ratio
+            irect = ar.argsort()
+            self.img_files_rgb = [self.img_files_rgb[i] for i in irect]
+            self.img_files_ir = [self.img_files_ir[i] for i in irect]       # the RGB order, applied to both lists
+            self.label_files_rgb = [self.label_files_rgb[i] for i in irect]
+            self.label_files_ir = [self.label_files_ir[i] for i in irect]
+            self.labels_rgb = [self.labels_rgb[i] for i in irect]
+            self.shapes_rgb = s[irect]  # wh
+            ar = ar[irect]
+
+            # Set training image shapes
+            shapes = [[1, 1]] * nb
+            for i in range(nb):
+                ari = ar[bi == i]
+                mini, maxi = ari.min(), ari.max()
+                if maxi < 1:
+                    shapes[i] = [maxi, 1]
+                elif mini > 1:
+                    shapes[i] = [1, 1 / mini]
+
+            self.batch_shapes_rgb = np.ceil(np.array(shapes) * img_size / stride + pad).astype(int) * stride
+
+        # the INTER_AREA resize of cft_pair_batch_u8 reduces by at most CFT_PAIR_MAX_REDUCTION per axis: say so before any work
+        for f, (w0, h0) in zip(self.img_files_rgb, self.shapes_rgb.astype(int)):
+            r = img_size / max(h0, w0)
+            if r < 1 and (int(h0 * r) * PAIR_MAX_REDUCTION < h0 or int(w0 * r) * PAIR_MAX_REDUCTION < w0):
+                raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={img_size} would reduce it by more than {PAIR_MAX_REDUCTION}x per axis, '
+                                 f'which cft_pair_batch_u8 does not do; use a larger img_size (about {-(-max(h0, w0) // PAIR_MAX_REDUCTION)} or more) or smaller images')
+
+        self.imgs_rgb = [None] * n      # cache_images: the decoded originals, HWC RGB uint8 CUDA tensors
+        self.imgs_ir = [None] * n
+        self.labels = self.labels_rgb
+        self.shapes = self.shapes_rgb
+        self.indices = self.indices_rgb
+
+    def __len__(self):
+        return len(self.img_files_rgb)
+
+    def pair_geometry(self, index):
+        """Where pair ``index`` lands in its batch: ``(h0, w0, h, w, top, left, mode, (H, W), ratio, pad)`` - the size arithmetic of
+        load_image_rgb_ir (:1361-1367) and of ``letterbox(auto=False, scaleup=False)`` (:1205-1207).  ``ratio`` is the letterbox's own:
+        (1, 1) for every shape this class builds, and then ``(h, w)`` is what lands at ``(top, left)``; ``build_descriptors`` checks it."""
+        w0, h0 = (int(v) for v in self.shapes_rgb[index])
+        r = self.img_size / max(h0, w0)  # ratio
+        h, w = (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
+        mode = PAIR_COPY if r == 1 else (PAIR_AREA if r < 1 else PAIR_LINEAR)
+        shape = self.batch_shapes_rgb[self.batch_rgb[index]] if self.rect else self.img_size  # final letterboxed shape
+        new_unpad, ratio, pad, (top, bottom, left, right) = letterbox_geometry((h, w), shape, auto=False, scaleup=False)
+        return h0, w0, h, w, top, left, mode, (new_unpad[1] + top + bottom, new_unpad[0] + left + right), ratio, pad
+
+    def item_targets(self, index):
+        """``(labels_out [nL, 6] float32 with column 0 zero, shapes)`` of ``__getitem__`` (:1209-1213, :1243-1247, :1266-1268)."""
+        h0, w0, h, w, top, left, mode, (H, W), ratio, pad = self.pair_geometry(index)
+        shapes = (h0, w0), ((h / h0, w / w0), pad)  # for COCO mAP rescaling
+        labels = self.labels_rgb[index].copy()
+        if labels.size:  # normalized xywh to pixel xyxy format
+            labels[:, 1:] = xywhn2xyxy(labels[:, 1:], ratio[0] * w, ratio[1] * h, padw=pad[0], padh=pad[1])
+        nL = len(labels)  # number of labels
+        if nL:
+            labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])  # convert xyxy to xywh
+            labels[:, [2, 4]] /= H  # normalized height 0-1
+            labels[:, [1, 3]] /= W  # normalized width 0-1
+        labels_out = torch.zeros((nL, 6))
+        if nL:
+            labels_out[:, 1:] = torch.from_numpy(labels)
+        return labels_out, shapes
+
+    def batch_targets(self, indices):
+        """``(targets [nt, 6] float32 CPU, paths, shapes)`` of one batch: ``item_targets`` + the reference's ``collate_fn`` (:1284-1288)."""
+        label, shapes = zip(*(self.item_targets(i) for i in indices))
+        for i, l in enumerate(label):
+            l[:, 0] = i  # add target image index for build_targets()
+        return torch.cat(label, 0), tuple(self.img_files_rgb[i] for i in indices), shapes
+
+    def build_descriptors(self, indices, flip=0):
+        """The table of cft_pair_batch_u8 for one batch, source pointers and strides left zero: ``(PAIR_DESC array [B], (H, W))``.
+        Raises LetterboxResizes if the letterbox would resize a pair again (never, for the shapes this class builds)."""
+        desc = np.zeros(len(indices), dtype=PAIR_DESC)
+        HW = None
+        for row, index in zip(desc, indices):
+            h0, w0, h, w, top, left, mode, hw, ratio, _ = self.pair_geometry(index)
+            if ratio != (1.0, 1.0):
+                raise LetterboxResizes(f"pair {index}: the letterbox would resize {w}x{h} again (ratio {ratio}); cft_pair_batch_u8 has one resize stage")
+            if HW is not None and hw != HW:
+                raise AssertionError(f"pair {index}: letterbox {hw} differs from its batch's {HW}")
+            HW = hw
+            row["h0"], row["w0"], row["h"], row["w"], row["top"], row["left"], row["mode"], row["flip"] = h0, w0, h, w, top, left, mode, flip
+        return desc, HW
+
+    def load_pair(self, index):
+        """The decoded originals of one pair, HWC RGB uint8 numpy arrays; checks them against the scanned shape."""
+        rgb, ir = decode_image(self.img_files_rgb[index]), decode_image(self.img_files_ir[index])
+        w0, h0 = (int(v) for v in self.shapes_rgb[index])
+        for im, f in ((rgb, self.img_files_rgb[index]), (ir, self.img_files_ir[index])):
+            if im.shape != (h0, w0, 3):
+                raise ValueError(f'{f}: decoded to {im.shape[1]}x{im.shape[0]}, scanned as {w0}x{h0}')
+        return rgb, ir
+
+
+def pair_batch(desc, out, color=114):
+    """Launch cft_pair_batch_u8: ``desc`` is a filled PAIR_DESC array (host), ``out`` the uint8 CUDA [B, 6, H, W] batch to write.
+    The device copy of the table is made on the current stream."""
+    from ..ops import pair_batch_u8
+    desc = np.ascontiguousarray(desc)
+    host = torch.from_numpy(desc.view(np.uint8).reshape(len(desc), -1)).pin_memory()
+    dev = host.to(out.device, non_blocking=True)
+    pair_batch_u8(dev, host, out, color)
+    return out
+
+
+def assemble_batch(dataset, indices, device, sources=None):
+    """One batch assembled directly: decode (or take ``sources``, a list of (rgb, ir) HWC RGB uint8 CUDA tensors), upload, one launch.
+    Returns the uint8 [B, 6, H, W] CUDA tensor.  The loader below does the same with staging buffers and prefetch."""
+    if sources is None:
+        sources = [tuple(torch.from_numpy(a).to(device) for a in dataset.load_pair(i)) for i in indices]
+    try:
+        desc, (H, W) = dataset.build_descriptors(indices)
+    except LetterboxResizes:
+        return assemble_batch_by_pair(dataset, indices, sources)
+    _fill_sources(desc, sources)
+    out = torch.empty((len(indices), 6, H, W), dtype=torch.uint8, device=device)
+    return pair_batch(desc, out)
+
+
+def assemble_batch_by_pair(dataset, indices, sources):
+    """A batch whose letterbox resizes again, pair by pair as the reference does it: the load_image_rgb_ir resize alone (one
+    cft_pair_batch_u8 launch per pair, no border), then the existing ``letterbox_pair`` (two cft_letterbox_u8 launches) into the pair's
+    block of the batch.  ``sources``: (rgb, ir) HWC RGB uint8 CUDA tensors.  Runs on the current stream."""
+    out = None
+    for k, (index, pair) in enumerate(zip(indices, sources)):
+        h0, w0, h, w, _, _, mode, (H, W), _, _ = dataset.pair_geometry(index)
+        desc = np.zeros(1, dtype=PAIR_DESC)
+        row = desc[0]
+        row["h0"], row["w0"], row["h"], row["w"], row["mode"], row["flip"] = h0, w0, h, w, mode, 1   # RGB in, BGR planes out
+        _fill_sources(desc, [pair])
+        w4 = (w + 3) & ~3                                           # the kernel writes whole dwords of a row
+        chw = pair_batch(desc, torch.empty((1, 6, h, w4), dtype=torch.uint8, device=pair[0].device))[0, :, :, :w]
+        bgr, ir = chw[:3].permute(1, 2, 0).contiguous(), chw[3:].permute(1, 2, 0).contiguous()      # HWC BGR, what letterbox_pair takes
+        if out is None:
+            out = torch.empty((len(indices), 6, H, W), dtype=torch.uint8, device=pair[0].device)
+        shape = dataset.batch_shapes_rgb[dataset.batch_rgb[index]] if dataset.rect else dataset.img_size
+        letterbox_pair(bgr, ir, tuple(int(v) for v in shape) if dataset.rect else shape, auto=False, scaleup=False, out=out[k])
+    return out
+
+
+def _fill_sources(desc, sources):
+    for row, (rgb, ir) in zip(desc, sources):
+        for t in (rgb, ir):
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.stride(2) != 1 or t.stride(1) != 3 or not t.is_cuda:
+                raise ValueError("pair sources must be HWC uint8 CUDA tensors with contiguous pixels")
+            if tuple(t.shape[:2]) != (int(row["h0"]), int(row["w0"])):
+                raise ValueError(f"pair source is {tuple(t.shape[:2])}, the table says {(int(row['h0']), int(row['w0']))}")
+        row["src_rgb"], row["src_ir"], row["stride_rgb"], row["stride_ir"] = rgb.data_ptr(), ir.data_ptr(), rgb.stride(0), ir.stride(0)
+
+
+class _Slot:
+    """One of the loader's two staging sets: pinned host bytes, their device copy, the table, and the two events that order them."""
+
+    def __init__(self):
+        self.pinned = self.staged = self.desc_host = self.desc_dev = None
+        self.ready = self.consumed = None       # upload finished (side stream) / batch assembled (consumer stream)
+
+    def reserve(self, nbytes, nrows, device):
+        if self.ready is not None:
+            self.ready.synchronize()             # the previous upload out of these pinned bytes has finished
+        if nbytes and (self.pinned is None or self.pinned.numel() < nbytes):
+            self.pinned = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            self.staged = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        if self.desc_host is None or self.desc_host.shape[0] < nrows:
+            self.desc_host = torch.empty((nrows, PAIR_DESC.itemsize), dtype=torch.uint8).pin_memory()
+            self.desc_dev = torch.empty((nrows, PAIR_DESC.itemsize), dtype=torch.uint8, device=device)
+
+
+class PairLoader:
+    """The iterable ``create_dataloader_rgb_ir`` returns: yields ``(img6 uint8 cuda [B, 6, H, W], targets float32 CPU [nt, 6], paths,
+    shapes)`` per batch, in dataset order.  While a batch is in use the next one is decoded (PIL, a pool of ``workers`` threads),
+    staged into a reused pinned buffer and uploaded on a side stream; an event recorded there is what the consumer stream waits on
+    before the batch's single cft_pair_batch_u8 launch, and an event recorded after that launch is what the side stream waits on
+    before it overwrites the slot's table and staging buffer two batches later (cached batches included: they reuse the table)."""
+
+    def __init__(self, dataset, batch_size, workers=8, rank=-1, world_size=1, device=None):
+        self.dataset = dataset
+        self.batch_size = max(1, min(batch_size, len(dataset)))
+        self.workers = max(1, min(int(workers), MAX_DECODE_THREADS))
+        nb = (len(dataset) + self.batch_size - 1) // self.batch_size
+        if rank >= 0:
+            from ..distributed import shard_bounds
+            self.batch_range = range(*shard_bounds(nb, rank, world_size))
+        else:
+            self.batch_range = range(nb)
+        self.device = torch.device(device if device is not None else "cuda")
+        self._side = None
+        self._slots = (_Slot(), _Slot())
+
+    def __len__(self):
+        return len(self.batch_range)
+
+    def batch_indices(self, b):
+        return list(range(b * self.batch_size, min((b + 1) * self.batch_size, len(self.dataset))))
+
+    def _stage(self, b, slot, pool):
+        """Decode and upload batch ``b`` (side stream); returns what ``_assemble`` needs."""
+        ds, indices = self.dataset, self.batch_indices(b)
+        try:
+            desc, HW = ds.build_descriptors(indices)
+        except LetterboxResizes:                         # assembled pair by pair (assemble_batch_by_pair): only the sizes are checked here
+            desc, HW = np.zeros(len(indices), dtype=PAIR_DESC), None
+            for row, index in zip(desc, indices):
+                row["h0"], row["w0"] = ds.pair_geometry(index)[:2]
+        cached = all(ds.imgs_rgb[i] is not None for i in indices)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            # Whatever this does to the slot - the table always, the staging buffer when it is reused - comes after the launch that read
+            # the slot two batches ago: the consumer stream may be many batches behind the host.
+            if slot.consumed is not None:
+                self._side.wait_event(slot.consumed)
+            if cached:
+                sources = [(ds.imgs_rgb[i], ds.imgs_ir[i]) for i in indices]
+                _fill_sources(desc, sources)
+                slot.reserve(0, len(indices), self.device)
+                staged = None
+            else:
+                pairs = list(pool.map(ds.load_pair, indices))
+                offs, total = [], 0
+                for rgb, ir in pairs:
+                    offs.append((total, total + _align16(rgb.nbytes)))
+                    total += _align16(rgb.nbytes) + _align16(ir.nbytes)
+                slot.reserve(total, len(indices), self.device)
+                if ds.cache_images:                      # these bytes stay: the batch's originals live in a buffer of their own
+                    staged = torch.empty(total, dtype=torch.uint8, device=self.device)
+                else:
+                    staged = slot.staged
+                host = slot.pinned.numpy()
+                for (o_rgb, o_ir), (rgb, ir) in zip(offs, pairs):
+                    host[o_rgb:o_rgb + rgb.nbytes] = rgb.reshape(-1)
+                    host[o_ir:o_ir + ir.nbytes] = ir.reshape(-1)
+                staged[:total].copy_(slot.pinned[:total], non_blocking=True)
+                sources = []
+                for (o_rgb, o_ir), (rgb, ir) in zip(offs, pairs):
+                    sources.append((staged[o_rgb:o_rgb + rgb.nbytes].view(rgb.shape), staged[o_ir:o_ir + ir.nbytes].view(ir.shape)))
+                _fill_sources(desc, sources)
+                if ds.cache_images:
+                    for i, (t_rgb, t_ir) in zip(indices, sources):
+                        ds.imgs_rgb[i], ds.imgs_ir[i] = t_rgb, t_ir
+            slot.desc_host[:len(indices)].numpy()[:] = desc.view(np.uint8).reshape(len(indices), -1)
+            slot.desc_dev[:len(indices)].copy_(slot.desc_host[:len(indices)], non_blocking=True)
+            slot.ready = torch.cuda.Event()
+            slot.ready.record(self._side)
+        return indices, HW, staged, sources
+
+    def _assemble(self, slot, indices, HW, staged, sources):
+        from ..ops import pair_batch_u8
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(slot.ready)
+        if HW is None:                                   # the letterbox resizes again: the per-image path
+            out = assemble_batch_by_pair(self.dataset, indices, sources)
+        else:
+            out = torch.empty((len(indices), 6, HW[0], HW[1]), dtype=torch.uint8, device=self.device)
+            pair_batch_u8(slot.desc_dev[:len(indices)], slot.desc_host[:len(indices)], out, 114)
+        slot.consumed = torch.cuda.Event()
+        slot.consumed.record(cur)
+        slot.desc_dev.record_stream(cur)                 # allocated on the side stream, read on this one
+        if staged is not None:
+            staged.record_stream(cur)
+        return out
+
+    def __iter__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        batches = list(self.batch_range)
+        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
+            nxt = stager.submit(self._stage, batches[0], self._slots[0], pool) if batches else None
+            for k, b in enumerate(batches):
+                staged = nxt.result()
+                slot = self._slots[k % 2]
+                # the next batch decodes and uploads while this one is assembled and used
+                nxt = stager.submit(self._stage, batches[k + 1], self._slots[(k + 1) % 2], pool) if k + 1 < len(batches) else None
+                img = self._assemble(slot, *staged)
+                targets, paths, shapes = self.dataset.batch_targets(staged[0])
+                yield img, targets, paths, shapes
+
+
+def _align16(n):
+    return (n + 15) & ~15
+
+
+def create_dataloader_rgb_ir(path1, path2, imgsz, batch_size, stride, opt, hyp=None, augment=False, cache=False, pad=0.0, rect=False,
+                             rank=-1, world_size=1, workers=8, image_weights=False, quad=False, prefix=''):
+    """The reference's ``create_dataloader_rgb_ir`` (utils/datasets.py:223-257) for the non-augmented form: returns ``(loader, dataset)``.
+    ``opt`` is read for ``single_cls`` only; the loader is a ``PairLoader`` (a plain iterable with ``__len__``), and with ``rank >= 0``
+    it yields that rank's contiguous range of batches (``distributed.shard_bounds``)."""
+    if quad:
+        raise NotImplementedError("create_dataloader_rgb_ir: quad=True (collate_fn4) belongs to augmented training and is not implemented")
+    dataset = LoadMultiModalImagesAndLabels(path1, path2, imgsz, batch_size,
+                                            augment=augment,  # augment images
+                                            hyp=hyp,  # augmentation hyperparameters
+                                            rect=rect,  # rectangular training
+                                            cache_images=cache,
+                                            single_cls=opt.single_cls,
+                                            stride=int(stride),
+                                            pad=pad,
+                                            image_weights=image_weights,
+                                            prefix=prefix)
+    return PairLoader(dataset, batch_size, workers=workers, rank=rank, world_size=world_size), dataset

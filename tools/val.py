@@ -1,0 +1,90 @@
+"""Validate a checkpoint on a paired RGB + IR dataset on disk: the command-line form of the reference's test.py.
+
+    python tools/val.py DATA.yaml WEIGHTS.pt [--img-size 640] [--batch-size 32] [--single-cls] [--save-txt] [--save-json] [--verbose]
+
+DATA.yaml holds ``val_rgb`` and ``val_ir`` (directories or *.txt lists; relative paths are taken from the yaml's directory), ``nc``
+and ``names``.  The loader is built as test.py builds it (:86-94: ``rect=True, pad=0.5``, the model's largest stride), every batch is
+one cft_pair_batch_u8 launch, ``evaluate`` does the rest on the GPU, and the table printed is test.py's (:100, :239-245).
+Every label class must be below ``nc`` unless ``--single-cls`` is given (test.py asserts the same of its data yaml); the check runs
+before the first batch.  ``--seeded CFG`` validates a seeded ``models/configs.py`` network instead of a checkpoint: a run without
+weights, e.g. on tests/golden/dataset/data.yaml, whose labels hold a class >= nc on purpose and so need ``--single-cls``."""
+import argparse
+import os
+import sys
+from types import SimpleNamespace
+
+import torch
+import yaml
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import msod_amd  # noqa: E402,F401
+from msod_amd.evaluate import evaluate  # noqa: E402
+from msod_amd.utils.datasets import create_dataloader_rgb_ir  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("data")
+    ap.add_argument("weights", nargs="?")
+    ap.add_argument("--seeded", metavar="CFG", help="a named config with seeded weights instead of a checkpoint")
+    ap.add_argument("--img-size", type=int, default=640)
+    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--conf-thres", type=float, default=0.001)
+    ap.add_argument("--iou-thres", type=float, default=0.6)
+    ap.add_argument("--single-cls", action="store_true")
+    ap.add_argument("--save-txt", action="store_true")
+    ap.add_argument("--save-json", action="store_true")
+    ap.add_argument("--save-dir", default="runs/val")
+    ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--verbose", action="store_true")
+    opt = ap.parse_args(argv)
+    if (opt.weights is None) == (opt.seeded is None):
+        ap.error("give WEIGHTS or --seeded CFG")
+
+    with open(opt.data) as f:
+        data = yaml.safe_load(f)
+    base = os.path.dirname(os.path.abspath(opt.data))
+    resolve = lambda p: [resolve(x) for x in p] if isinstance(p, list) else (p if os.path.isabs(p) else os.path.join(base, p))  # noqa: E731
+    nc = 1 if opt.single_cls else int(data["nc"])
+
+    device = torch.device("cuda:0")
+    if opt.seeded:
+        from msod_amd.models.configs import named_config
+        from msod_amd.models.yolo_test import Model
+        from msod_amd.utils.seeded import seeded_state_dict
+        model = Model(named_config(opt.seeded))
+        model.load_state_dict(seeded_state_dict(model.state_dict(), seed=7))
+    else:
+        from msod_amd import compat
+        model = compat.attempt_load(opt.weights, map_location="cpu")
+    model = model.to(device).eval()
+    gs = max(int(model.stride.max()), 32)  # grid size (max stride)
+    names = data.get("names") or [str(i) for i in range(nc)]
+
+    loader, dataset = create_dataloader_rgb_ir(resolve(data["val_rgb"]), resolve(data["val_ir"]), opt.img_size, opt.batch_size, gs,
+                                               SimpleNamespace(single_cls=opt.single_cls), pad=0.5, rect=True,
+                                               workers=opt.workers, prefix="val: ")
+    if not opt.single_cls:
+        for f, l in zip(dataset.label_files_rgb, dataset.labels):
+            if len(l) and l[:, 0].max() >= nc:
+                sys.exit(f"val: {f} holds class {int(l[:, 0].max())}, but {opt.data} says nc: {nc} (classes 0..{nc - 1}); "
+                         f"fix the labels or nc, or pass --single-cls")
+    details = {}
+    evaluate(model, loader, nc, conf_thres=opt.conf_thres, iou_thres=opt.iou_thres, single_cls=opt.single_cls, save_txt=opt.save_txt,
+             save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json) else None, details=details)
+    res = details["result"]
+
+    print(('%20s' + '%12s' * 7) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.75', 'mAP@.5:.95'))
+    pf = '%20s' + '%12i' * 2 + '%12.3g' * 5  # print format
+    print(pf % ('all', res.seen, int(res.nt.sum()), res.mp, res.mr, res.map50, res.map75, res.map))
+    if (opt.verbose or nc < 50) and nc > 1 and len(res.ap_class):
+        ap = res.ap
+        for i, c in enumerate(res.ap_class):
+            print(pf % (names[c] if c < len(names) else str(c), res.seen, res.nt[c], res.p[i], res.r[i], ap[i, 0], ap[i, 5], ap[i].mean()))
+    if opt.save_txt or opt.save_json:
+        print(f"Results saved to {opt.save_dir}")
+    return res
+
+
+if __name__ == "__main__":
+    main()
