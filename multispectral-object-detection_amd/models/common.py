@@ -27,6 +27,7 @@ statistics and running-stat updates (``cft_batchnorm_train`` after an un-folded 
 MLP (``cft_dropout``, counter-based masks), ``Detect`` returning the raw list.  No autograd graph is built.
 """
 import math
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -118,7 +119,7 @@ def invalidate_packed(root):
     for m in root.modules():
         m.__dict__.pop("_cft_cache", None)
         m.__dict__.pop("_cft_cache_train", None)
-        m.__dict__.pop("_res_chain_cache", None)
+        m.__dict__.pop("_plan_cache", None)
         if "_graphs" in m.__dict__:
             m.__dict__["_graphs"].clear()
         m.__dict__.pop("_wlist", None)
@@ -225,6 +226,17 @@ class Bottleneck(nn.Module):
         return self.cv2(self.cv1(x), residual=x if self.add else None, out=out)
 
 
+# C3.launch_plan.  front: "chained" (the Conv handed over and cv1|cv2 as one ops.conv2d_chain kernel), "separate" (that conv, then cv1|cv2) or
+# None (no conv was handed over); split: cv1 and cv2 as two launches (training); steps: (form, j) over the Bottlenecks m[j], with y the
+# input (and shortcut) of the current Bottleneck and h its cv1 output:
+#   "block"     y = m[j](y)                               the Bottleneck's own forward (it picks the patch-resident kernel where it can)
+#   "cv1"       h = m[j].cv1(y)
+#   "cv2"       y = m[j].cv2(h) (+ y)                     the last one writes the concat buffer's first half
+#   "pair"      h = m[j + 1].cv1(m[j].cv2(h))             one kernel (ops.conv2d_chain); neither Bottleneck has a shortcut
+#   "pair_res"  y = m[j].cv2(h) + y; h = m[j + 1].cv1(y)  one kernel (ops.conv2d_chain_res)
+C3Plan = namedtuple("C3Plan", "front split steps")
+
+
 class C3(_Packed):
     """CSP bottleneck with 3 convolutions (reference models/common.py:131-143):
     cv3(cat(m(cv1(x)), cv2(x))).  cv1 and cv2 read the same input, so they run as one GEMM whose
@@ -243,93 +255,98 @@ class C3(_Packed):
         w2, b2 = _folded(self.cv2)
         return ops.pack_conv(torch.cat([w1, w2], 0), torch.cat([b1, b2], 0), dtype, device=device)
 
-    def forward(self, x, out=None):
-        c_ = self.cv1.conv.out_channels
-        if _act_code(self.cv1.act) != _act_code(self.cv2.act):
-            raise NotImplementedError("C3.cv1 and C3.cv2 must share an activation")
-        if self.training:        # batch statistics are per BatchNorm: cv1 and cv2 run separately into the concat buffer
-            x = resolve(x)
-            B, _, H, W = x.shape
-            cat = ops.new_nhwc(B, H, W, 2 * c_, x.dtype, x.device)
-            self.cv1(x, out=cat[:, :c_])
-            self.cv2(x, out=cat[:, c_:])
-        else:
-            src = resolve(x.x) if isinstance(x, PendingConv) else resolve(x)
-            pk, act = self._packed(src.dtype, src.device), _act_code(self.cv1.act)
-            pk1 = x.conv._packed(src.dtype, src.device) if isinstance(x, PendingConv) else None
-            if pk1 is not None and _act_code(x.conv.act) == ACT_SILU and ops.conv2d_chain_ok(src, pk1, pk):
-                cat = ops.conv2d_chain(src, pk1, pk, act)       # the Conv in front of this C3 was left to it: one kernel for both
-            else:
-                x = x.conv(src) if pk1 is not None else src
-                cat = ops.conv2d(x, pk, act)     # [B, 2c_, H, W]
-        head = cat[:, :c_]
-        y = head
-        n = len(self.m)
-        if self.chain and self.chain_pairs and n >= 2 and not self.training and self._res_chainable(head):
-            # WITH shortcuts (backbone C3s, 256 channels): Bottleneck j's output is the next shortcut AND the input of Bottleneck j + 1's 1x1 -
-            # cv2[j] (+ shortcut) and cv1[j + 1] run as one launch (ops.conv2d_chain_res): n + 1 launches instead of 2 n, no re-read of y
-            h = self.m[0].cv1(y)
-            for j in range(n - 1):
-                blk, nxt = self.m[j], self.m[j + 1]
-                y, h = ops.conv2d_chain_res(h, blk.cv2._packed(h.dtype, h.device), y, nxt.cv1._packed(h.dtype, h.device), _act_code(nxt.cv1.act))
-            self.m[n - 1].cv2(h, residual=y, out=head)
-            return self.cv3(cat, out=out)
-        # Without shortcuts a Bottleneck's output has ONE reader, the next Bottleneck's 1x1 (reference models/common.py:108-109, :142):
-        # cv2[j] + cv1[j + 1] then run as one launch (ops.conv2d_chain) and the tensor between the two Bottlenecks never exists.
-        can = [self.chain and self.chain_pairs and j + 1 < n and self._chainable(self.m[j], self.m[j + 1], head) for j in range(n)]
-        hidden = None              # cv1 output of Bottleneck j, already produced by the chained launch of Bottleneck j - 1
-        for j, blk in enumerate(self.m):
-            dst = head if j == n - 1 else None
-            if hidden is None and not can[j]:
-                y = blk(y, out=dst)
-                continue
-            h = hidden if hidden is not None else blk.cv1(y)
-            if can[j]:
-                nxt = self.m[j + 1]
-                hidden = ops.conv2d_chain(h, blk.cv2._packed(h.dtype, h.device), nxt.cv1._packed(h.dtype, h.device), _act_code(nxt.cv1.act))
-            else:
-                hidden, y = None, blk.cv2(h, out=dst)
-        return self.cv3(cat, out=out)
-
     chain = True                   # Model.chain_convs switches it (A/B)
-    chain_pairs = True             # the Bottleneck-pair chains (3x3 of Bottleneck j + 1x1 of Bottleneck j + 1) on their own (A/B: bench.py --no-pair-chain)
+    chain_pairs = True             # the Bottleneck-pair chains (3x3 of Bottleneck j + 1x1 of Bottleneck j + 1) on their own (Model.chain_pairs; bench.py --no-pair-chain)
 
-    def _res_chainable(self, y):
-        """Every Bottleneck has a shortcut and (cv2[j], cv1[j + 1]) is a pair ``ops.conv2d_chain_res`` takes on tensors shaped like ``y``."""
-        if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype in (torch.bfloat16, torch.float16)):
-            return False
-        # the decision depends on the pixel grid and the type (h and y1 are dense tensors of this shape), on the size heuristic that tests
-        # and A/B runs patch, and on the packed weights: invalidate_packed drops the cache with them
-        key = (tuple(y.shape), y.dtype, y.device, ops.CHAIN_RES_MIN_ROWS)
-        cache = self.__dict__.setdefault("_res_chain_cache", {})
+    def launch_plan(self, B, H, W, dtype, front=None, ld_in=None):
+        """The ``C3Plan`` of a forward on a [B, *, H, W] tensor of ``dtype`` with ``ld_in`` channels per pixel (None: dense); ``front``: the
+        ``Conv`` left to this C3 as a ``PendingConv`` - the tensor is then THAT conv's input.  Decided from the geometry and the packed
+        weights' shapes alone (a CPU-resident module answers too) and cached: the key holds everything the decision reads."""
+        key = (front, B, H, W, ld_in, dtype, self.training, self.chain, self.chain_pairs, ops.CHAIN_RES_MIN_ROWS)
+        cache = self.__dict__.setdefault("_plan_cache", {})          # (invalidate_packed drops it)
         if key not in cache:
             if len(cache) > 16:
                 cache.clear()
-            cache[key] = self._res_chainable_uncached(y)
+            cache[key] = self._plan(B, H, W, dtype, front, ld_in)
         return cache[key]
 
-    def _res_chainable_uncached(self, y):
-        for j, blk in enumerate(self.m):
-            if not blk.add or _act_code(blk.cv1.act) != ACT_SILU or _act_code(blk.cv2.act) != ACT_SILU:
-                return False
-            pk1, pk2 = blk.cv1._packed(y.dtype, y.device), blk.cv2._packed(y.dtype, y.device)
-            if ops.bottleneck_fusable(y, pk1, pk2, ACT_SILU, ACT_SILU):
-                return False               # 64 / 128 channels: the patch-resident Bottleneck kernel
-            if j + 1 < len(self.m) and not ops.conv2d_chain_res_ok_geometry(y.shape[0], y.shape[2], y.shape[3], y.dtype, pk2,
-                                                                            self.m[j + 1].cv1._packed(y.dtype, y.device)):
-                return False               # (dense h / y1 of this pixel grid - what the launch below passes; ADVICE r5)
-        return True
+    def _plan(self, B, H, W, dtype, front, ld_in):
+        n = len(self.m)
+        blocks = tuple(("block", j) for j in range(n))
+        if self.training:        # batch statistics are per BatchNorm: cv1 and cv2 run separately into the concat buffer
+            return C3Plan(None if front is None else "separate", True, blocks)
+        dev = self.cv1.conv.weight.device
+        how = None
+        if front is not None:    # chained: SiLU and a pair cft_conv2d_chain_ok takes with the source's real ld
+            ok = _act_code(front.act) == ACT_SILU and ops.conv2d_chain_ok_geometry(B, H, W, dtype, front._packed(dtype, dev), self._packed(dtype, dev), ldx=ld_in)
+            how = "chained" if ok else "separate"
+            H, W = ops.conv_out_size(H, W, front.conv.kernel_size[0], front.conv.stride[0])
+        if not (self.chain and self.chain_pairs and n >= 2 and dtype in (torch.bfloat16, torch.float16)):
+            return C3Plan(how, False, blocks)
+        pks = [(b.cv1._packed(dtype, dev), b.cv2._packed(dtype, dev)) for b in self.m]
+        acts = [(_act_code(b.cv1.act), _act_code(b.cv2.act)) for b in self.m]
+        # 64 / 128 channels: the patch-resident kernel of Bottleneck.forward is the better fusion, such a Bottleneck is never chained
+        y = torch.empty((B, self.cv1.conv.out_channels, H, W), dtype=dtype, device="meta")       # (its shape and type are all that is read)
+        own = [ops.bottleneck_fusable(y, *pk, *act) for pk, act in zip(pks, acts)]
+        # WITH shortcuts (backbone C3s, 256 channels): Bottleneck j's output is the next shortcut AND the input of Bottleneck j + 1's 1x1 -
+        # cv2[j] (+ shortcut) and cv1[j + 1] run as one launch: n + 1 launches instead of 2 n, no re-read of y.  All pairs or none; h and
+        # y1 are dense tensors of this pixel grid (ADVICE r5)
+        if (all(b.add for b in self.m) and all(a == (ACT_SILU, ACT_SILU) for a in acts) and not any(own)
+                and all(ops.conv2d_chain_res_ok_geometry(B, H, W, dtype, pks[j][1], pks[j + 1][0]) for j in range(n - 1))):
+            return C3Plan(how, False, (("cv1", 0),) + tuple(("pair_res", j) for j in range(n - 1)) + (("cv2", n - 1),))
+        # Without shortcuts a Bottleneck's output has ONE reader, the next Bottleneck's 1x1 (reference models/common.py:108-109, :142): cv2[j] +
+        # cv1[j + 1] then run as one launch and the tensor between the two Bottlenecks never exists.  Decided pair by pair
+        can = [j + 1 < n and not (self.m[j].add or self.m[j + 1].add or own[j]) and acts[j][1] == ACT_SILU
+               and ops.conv2d_chain_ok_geometry(B, H, W, dtype, pks[j][1], pks[j + 1][0]) for j in range(n)]
+        steps = []
+        for j in range(n):
+            entered = j > 0 and can[j - 1]          # cv1[j] already ran, in the chained launch of Bottleneck j - 1
+            if entered or can[j]:
+                steps += ([] if entered else [("cv1", j)]) + [("pair" if can[j] else "cv2", j)]
+            else:
+                steps.append(("block", j))
+        return C3Plan(how, False, tuple(steps))
 
-    def _chainable(self, blk, nxt, y):
-        """``blk.cv2`` (3x3) and ``nxt.cv1`` (1x1) can run as one kernel on tensors shaped like ``y``: inference, no shortcut on either
-        (``blk``'s output is then read by ``nxt.cv1`` only), SiLU, and a geometry the chained kernel takes."""
-        if self.training or blk.add or nxt.add or not (isinstance(y, torch.Tensor) and y.is_cuda) or _act_code(blk.cv2.act) != ACT_SILU:
-            return False
-        if ops.bottleneck_fusable(y, blk.cv1._packed(y.dtype, y.device), blk.cv2._packed(y.dtype, y.device),
-                                  _act_code(blk.cv1.act), _act_code(blk.cv2.act)):
-            return False               # 64 / 128 channels: the patch-resident Bottleneck kernel is the better fusion
-        return ops.conv2d_chain_ok_geometry(y.shape[0], y.shape[2], y.shape[3], y.dtype, blk.cv2._packed(y.dtype, y.device),
-                                            nxt.cv1._packed(y.dtype, y.device))
+    def forward(self, x, out=None):
+        c_ = self.cv1.conv.out_channels
+        act = _act_code(self.cv1.act)
+        if act != _act_code(self.cv2.act):
+            raise NotImplementedError("C3.cv1 and C3.cv2 must share an activation")
+        front = x.conv if isinstance(x, PendingConv) else None
+        x = resolve(x.x if front is not None else x)
+        B, _, H, W = x.shape
+        dt, dev = x.dtype, x.device
+        plan = self.launch_plan(B, H, W, dt, front, x.stride(3) if (x.stride(1) == 1 and x.stride(3) >= x.shape[1]) else None)
+        if plan.front == "chained":
+            cat = ops.conv2d_chain(x, front._packed(dt, dev), self._packed(dt, dev), act)    # one kernel for the Conv in front and cv1|cv2
+        else:
+            if front is not None:
+                x = front(x)
+            if plan.split:
+                B, _, H, W = x.shape
+                cat = ops.new_nhwc(B, H, W, 2 * c_, dt, dev)
+                self.cv1(x, out=cat[:, :c_])
+                self.cv2(x, out=cat[:, c_:])
+            else:
+                cat = ops.conv2d(x, self._packed(dt, dev), act)     # [B, 2c_, H, W]
+        head = cat[:, :c_]
+        y, h, last = head, None, len(self.m) - 1
+        for form, j in plan.steps:
+            blk, dst = self.m[j], (head if j == last else None)
+            if form == "block":
+                y = blk(y, out=dst)
+            elif form == "cv1":
+                h = blk.cv1(y)
+            elif form == "cv2":
+                y = blk.cv2(h, residual=y if blk.add else None, out=dst)
+            else:
+                nxt = self.m[j + 1].cv1
+                pk2, pk1, act1 = blk.cv2._packed(dt, dev), nxt._packed(dt, dev), _act_code(nxt.act)
+                if form == "pair":
+                    h = ops.conv2d_chain(h, pk2, pk1, act1)
+                else:
+                    y, h = ops.conv2d_chain_res(h, pk2, y, pk1, act1)
+        return self.cv3(cat, out=out)
 
 
 class SPP(nn.Module):
@@ -457,6 +474,34 @@ class Add2(nn.Module):
 
 
 # ------------------------------------------------------------------------------ CFT block
+class _ResidualStream:
+    """The fp32 residual stream ``x`` [rows, d] of the CFT blocks (``dtype``: what the GEMMs compute in).  It is updated in place by the
+    epilogue of the GEMM that adds to it - or, where ``split`` allows (each block sets it from its own switch: inference on the GPU) and
+    ``ops.splitk_choice`` splits that GEMM, the fp32 partial sums [s, rows, d] stay ``pending`` and the next LayerNorm folds them in, in a
+    fixed order (``ops.layernorm_reduce``: the next block's ln_input, or ln_f)."""
+
+    def __init__(self, x, dtype):
+        self.x, self.dtype, self.split, self.pending = x, dtype, False, None
+
+    def norm(self, gamma, beta, eps, out_dtype):
+        """LayerNorm(x) in ``out_dtype``, after folding what is pending into x."""
+        parts, self.pending = self.pending, None
+        if parts is not None:
+            return ops.layernorm_reduce(self.x, parts, gamma, beta, out_dtype, eps)
+        return ops.layernorm(self.x, gamma, beta, out_dtype, eps)
+
+    def add_linear(self, inp, pk, drop_p=0.0):
+        """x += dropout(linear(inp, pk))."""
+        if drop_p > 0:
+            z = ops.linear(inp, pk, out_dtype=torch.float32)
+            ops.dropout_(z, drop_p)
+            ops.add_rows_(self.x, z)
+        elif self.split and (splits := ops.splitk_choice(inp.shape[0], pk, inp.dtype)) > 1:
+            self.pending = ops.linear_splitk(inp, pk, splits)
+        else:
+            ops.linear(inp, pk, residual=self.x, out=self.x, out_dtype=torch.float32)
+
+
 class SelfAttention(_Packed):
     """Multi-head self-attention (reference models/common.py:430-513).  q/k/v projections run as
     one GEMM; heads are laid out at a padded width ``dkp`` so the attention kernel needs no tails."""
@@ -501,27 +546,18 @@ class SelfAttention(_Packed):
         out.flops_per_row = 2.0 * d * h * dk
         return qkv, out, dkp
 
-    def forward(self, x, attention_mask=None, attention_weights=None, residual=None, splitk=False, ntok=128):
-        """x: [B*ntok, d] in the compute dtype (``ntok`` tokens per image: 2 * vert_anchors * horz_anchors of the GPT).  Returns out_proj(attn) (+ residual, fp32, in place).  ``splitk`` (the transformer block's
-        inference path): returns the out_proj's fp32 split-K partial sums [s, rows, d] when ``ops.splitk_choice`` splits it (``residual`` is
-        then NOT updated - ``ops.layernorm_reduce`` does that), else None after the in-place update."""
+    def forward(self, x, attention_mask=None, attention_weights=None, stream=None, ntok=128):
+        """x: [B*ntok, d] in the compute dtype (``ntok`` tokens per image: 2 * vert_anchors * horz_anchors of the GPT).  Returns out_proj(attn); with
+        ``stream`` (the transformer block's ``_ResidualStream``) resid_drop(out_proj(attn)) is added to the stream instead and nothing is returned."""
         if attention_mask is not None or attention_weights is not None:
             raise NotImplementedError("attention_mask / attention_weights are unused by GPT (reference :497-500)")
         qkv_w, out_w, dkp = self._packed(x.dtype, x.device)
         B = x.shape[0] // ntok
         qkv = ops.linear(x, qkv_w)
         att = ops.attention(qkv, B, self.h, self.d_k, dkp, pdrop=self.attn_drop.p if self.training else 0.0, T=ntok)
-        if self.training and self.resid_drop.p > 0 and residual is not None:
-            proj = ops.linear(att, out_w, out_dtype=torch.float32)          # resid_drop(out_proj(.)) then the residual add
-            ops.dropout_(proj, self.resid_drop.p)
-            return ops.add_rows_(residual, proj)
-        if splitk and residual is not None and not self.training:
-            s_ = ops.splitk_choice(att.shape[0], out_w, att.dtype)
-            if s_ > 1:
-                return ops.linear_splitk(att, out_w, s_)         # fp32 partial sums; the caller's next LayerNorm folds them into ``residual``
-        out = ops.linear(att, out_w, residual=residual, out=residual,
-                         out_dtype=torch.float32 if residual is not None else None)
-        return None if splitk else out
+        if stream is None:
+            return ops.linear(att, out_w)
+        stream.add_linear(att, out_w, self.resid_drop.p if self.training else 0.0)
 
 
 class myTransformerBlock(_Packed):
@@ -548,37 +584,13 @@ class myTransformerBlock(_Packed):
 
     splitk = True        # inference: out_proj / fc2 as split-K GEMMs where ops.splitk_choice splits them (GPT.splitk switches all blocks; A/B)
 
-    def forward(self, x, compute_dtype=torch.bfloat16, pending=None, ntok=128):
-        """``pending``: fp32 split-K partial sums of the PREVIOUS block's fc2 that are not yet folded into ``x`` (or None).  Returns this
-        block's own pending partial sums (or None when its fc2 updated ``x`` in place); ``GPT.forward`` hands them to the next block /
-        ``ln_f``.  Each LayerNorm that follows a split GEMM is ``ops.layernorm_reduce``: x += partial sums (fixed order), then LayerNorm."""
-        fc1, fc2, ln = self._packed(compute_dtype, x.device)
-        split = self.splitk and not self.training and x.is_cuda
-
-        def norm(parts, g, b, eps):
-            if parts is not None:
-                return ops.layernorm_reduce(x, parts, g, b, compute_dtype, eps)
-            return ops.layernorm(x, g, b, compute_dtype, eps)
-        y = norm(pending, ln[0], ln[1], self.ln_input.eps)
-        parts = None
-        if split:
-            parts = self.sa(y, residual=x, splitk=True, ntok=ntok)   # x += out_proj(attention(LN(x))), or its partial sums
-        else:
-            self.sa(y, residual=x, ntok=ntok)
-        y = norm(parts, ln[2], ln[3], self.ln_output.eps)
-        hid = ops.linear(y, fc1, act=ACT_GELU)
-        pd = self.mlp[3].p if (self.training and len(self.mlp) > 3) else 0.0
-        if pd > 0:
-            z = ops.linear(hid, fc2, out_dtype=torch.float32)
-            ops.dropout_(z, pd)
-            ops.add_rows_(x, z)
-            return None
-        if split:
-            s_ = ops.splitk_choice(hid.shape[0], fc2, hid.dtype)
-            if s_ > 1:
-                return ops.linear_splitk(hid, fc2, s_)                     # folded into x by the next LayerNorm (next block's ln_input / ln_f)
-        ops.linear(hid, fc2, residual=x, out=x, out_dtype=torch.float32)  # x += fc2(gelu(fc1(LN(x))))
-        return None
+    def forward(self, stream, ntok=128):
+        """x += sa(LN(x)); x += mlp(LN(x)) on the ``_ResidualStream`` of ``GPT.forward``."""
+        fc1, fc2, ln = self._packed(stream.dtype, stream.x.device)
+        stream.split = self.splitk and not self.training and stream.x.is_cuda
+        self.sa(stream.norm(ln[0], ln[1], self.ln_input.eps, stream.dtype), stream=stream, ntok=ntok)
+        hid = ops.linear(stream.norm(ln[2], ln[3], self.ln_output.eps, stream.dtype), fc1, act=ACT_GELU)
+        stream.add_linear(hid, fc2, self.mlp[3].p if (self.training and len(self.mlp) > 3) else 0.0)
 
 
 class GPT(_Packed):
@@ -642,14 +654,10 @@ class GPT(_Packed):
         tok = ops.gpt_tokenize(rgb, ir, pos_emb, grid=grid)      # fp32 [B,T,C], pos_emb added
         if self.training:
             ops.dropout_(tok, self.drop.p)                       # self.drop(pos_emb + token_embeddings), reference :611
-        t2 = tok.view(B * T, C)
-        pending = None                                           # split-K partial sums of the last fc2, not yet folded into t2
+        stream = _ResidualStream(tok.view(B * T, C), dtype)
         for blk in self.trans_blocks:
-            pending = blk(t2, dtype, pending, ntok=T)
-        if pending is not None:
-            tok_f = ops.layernorm_reduce(t2, pending, lnf_w, lnf_b, torch.float32, self.ln_f.eps).view(B, T, C)
-        else:
-            tok_f = ops.layernorm(t2, lnf_w, lnf_b, torch.float32, self.ln_f.eps).view(B, T, C)
+            blk(stream, ntok=T)
+        tok_f = stream.norm(lnf_w, lnf_b, self.ln_f.eps, torch.float32).view(B, T, C)
         tok_f.anchor_grid = grid                                 # ops.token_grid: the consumers (Model's fused dual de-tokeniser) read it
         return PendingBilinear(tok_f, 0, H, W, dtype, grid), PendingBilinear(tok_f, 1, H, W, dtype, grid)
 

@@ -282,8 +282,8 @@ class Model(nn.Module):
     def chain_plan(self):
         """Indices of the ``Conv`` layers whose output is read by exactly one layer, the ``C3`` right behind them (``f == -1``): yaml
         rows 1, 3, 6, 8, 13, 15 of the x3 configs (the convs in front of SPP or Concat do not qualify).  Such a conv is handed to its
-        C3 un-run (``PendingConv``); the C3 issues both as one kernel when ``ops.conv2d_chain_ok`` accepts the pair (a conv of 128
-        or 256 output channels: rows 1, 3, 6, 8 of yolov5l), else it runs the conv itself."""
+        C3 un-run (``PendingConv``); the C3's launch plan (``C3.launch_plan``) issues both as one kernel when ``cft_conv2d_chain_ok``
+        accepts the pair (a conv of 128 or 256 output channels: rows 1, 3, 6, 8 of yolov5l), else it runs the conv itself."""
         return self.layer_graph().chain_plan
 
     def cft_fusion_plan(self):
@@ -319,6 +319,10 @@ class Model(nn.Module):
                           "Run producer / pointwise-consumer layer pairs as one ``cft_conv2d_chain`` kernel where eligible (default): the Conv handed to "
                           "the C3 behind it (``chain_plan``) and, inside a C3 without shortcuts, ``Bottleneck[j].cv2`` + ``Bottleneck[j+1].cv1``.  ``False`` "
                           "runs every layer as its own launch (A/B; bit-identical results).", push=(C3, "chain"))
+    chain_pairs = _switch("chain_pairs", True,
+                          "The chains inside a C3 on their own: ``Bottleneck[j].cv2`` (+ shortcut) + ``Bottleneck[j+1].cv1`` as one kernel where "
+                          "``C3.launch_plan`` finds the pair eligible (default).  ``False`` leaves only the Conv + cv1|cv2 chains (A/B; bit-identical results).",
+                          push=(C3, "chain_pairs"))
     splitk = _switch("splitk", True,
                      "Run the CFT blocks' out_proj / fc2 GEMMs as split-K launches where ``ops.splitk_choice`` splits them (default; the LayerNorm that "
                      "follows folds the fp32 partial sums into the residual stream in a fixed order).  ``False``: one launch per GEMM with the residual "

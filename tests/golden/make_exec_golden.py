@@ -50,6 +50,7 @@ def host_plans():
 
 
 # ---- traced walks: name -> what differs from (bf16, eval, every switch at its default, one plain model(x, x2)) ------------------------
+# (``c3_attrs``: set on every C3 instance; ``min_rows``: ops.CHAIN_RES_MIN_ROWS during the walk)
 def _x3(**kw):
     return dict(cfg=X3, shape=(4, 64, 96), **kw)
 
@@ -74,6 +75,11 @@ CASES = {
     # the only shape that reaches conv2d_chain, conv2d_chain_res and the shortcut-free pair chains (yolov5l widths)
     "cfg3-chains-two-lanes": dict(cfg="cfg3", shape=(2, 192, 256), min_rows=0),
     "cfg3-chains-one-lane": dict(cfg="cfg3", shape=(2, 192, 256), min_rows=0, attrs={"overlap_streams": False}),
+    "cfg3-default-heuristic": dict(cfg="cfg3", shape=(2, 192, 256)),
+    "cfg3-no-pair-chain": dict(cfg="cfg3", shape=(2, 192, 256), min_rows=0, c3_attrs={"chain_pairs": False}),
+    "cfg3-chains-fp16": dict(cfg="cfg3", shape=(2, 192, 256), min_rows=0, dtype=torch.float16),
+    "cfg3-chains-depth-first": dict(cfg="cfg3", shape=(4, 192, 256), min_rows=0, attrs={"depth_first": (2, None)}),
+    "cfg3-no-splitk": dict(cfg="cfg3", shape=(2, 192, 256), min_rows=0, attrs={"splitk": False}),
 }
 
 
@@ -88,6 +94,10 @@ def build_case(name, dev):
     model = model.to(dev).set_compute_dtype(case.get("dtype", torch.bfloat16))
     for k, v in case.get("attrs", {}).items():
         setattr(model, k, v)
+    for k, v in case.get("c3_attrs", {}).items():       # an attribute of every C3 instance (a switch that not every revision's Model knows)
+        for m in model.modules():
+            if type(m).__name__ == "C3":
+                setattr(m, k, v)
     if case.get("train"):
         model.train()
     if case.get("nms"):

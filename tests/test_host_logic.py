@@ -471,12 +471,206 @@ def test_prefix_segments_and_executor_switches():
     assert m.prefix_segments() == [(0, 4), (5, 9)] and m.prefix_segments(3) == [(0, 2), (5, 7)] and m.prefix_segments(2) == []
     assert Model(named_config("cfg1")).prefix_segments() == [(0, 4), (10, 14)]            # add-fusion: row 4 is also read by the Add
     assert Model(named_config("yolov5l_fusion_transformer_FLIR")).prefix_segments() == [(0, 2), (3, 5)]   # 4-GPT layout: GPT after P2
-    assert (m.depth_first, m.splitk, m.chain_convs, m.fuse_cft_outputs, m.plan_concats) == (None, True, True, True, True)
-    for name, value in (("depth_first", (8, None)), ("splitk", False), ("chain_convs", False),
+    assert (m.depth_first, m.splitk, m.chain_convs, m.chain_pairs, m.fuse_cft_outputs, m.plan_concats) == (None, True, True, True, True, True)
+    for name, value in (("depth_first", (8, None)), ("splitk", False), ("chain_convs", False), ("chain_pairs", False),
                         ("fuse_cft_outputs", False), ("plan_concats", False)):
         m._graphs["sentinel"] = object()
         setattr(m, name, value)
         assert getattr(m, name) == value and not m._graphs, name
+
+
+# ---- C3 launch plans (C3.launch_plan): cfg3's twelve C3s --------------------------------------------------------------------------
+C3_STRIDE = {2: 4, 7: 4, 4: 8, 9: 8, 14: 16, 16: 16, 22: 32, 25: 32, 35: 16, 39: 8, 42: 16, 45: 32}      # yaml row -> image pixels per cell
+
+
+def _blocks(n):
+    return tuple(("block", j) for j in range(n))
+
+
+def _res_chain(n):
+    return (("cv1", 0),) + tuple(("pair_res", j) for j in range(n - 1)) + (("cv2", n - 1),)
+
+
+PAIRS3 = (("cv1", 0), ("pair", 0), ("pair", 1), ("cv2", 2))
+
+
+def _c3_plans(model, B, Himg, Wimg, dtype, want=None):
+    """{row: (front, split, steps)} of every C3 of cfg3 for a B x Himg x Wimg image batch; ``want``: a restatement to hold each against."""
+    plans = {}
+    for i, stride in C3_STRIDE.items():
+        c3, front = model.model[i], (model.model[i - 1] if i - 1 in model.chain_plan() else None)
+        H, W = Himg // stride, Wimg // stride                  # the grid cv1|cv2 sees; a front conv (3x3, stride 2) reads twice that
+        k = 1 if front is None else front.conv.stride[0]
+        plans[i] = tuple(c3.launch_plan(B, H * k, W * k, dtype, front))
+        if want is not None:
+            assert plans[i] == want(c3, front, B, H, W, dtype), i
+    return plans
+
+
+def _restated_plan(c3, front, B, H, W, dtype):
+    """C3's launch rules restated independently of the planner: from the ``ops.*_geometry`` predicates on freshly packed weights (inference)."""
+    pk = lambda conv: ops.pack_conv(*ops.fold_bn(conv.conv.weight, conv.bn.weight, conv.bn.bias, conv.bn.running_mean, conv.bn.running_var,   # noqa: E731
+                                                 conv.bn.eps), dtype, s=conv.conv.stride[0])
+    how = None
+    if front is not None:
+        both = ops.pack_conv(torch.cat([c3.cv1.conv.weight, c3.cv2.conv.weight]), torch.zeros(2 * c3.cv1.conv.out_channels), dtype)
+        how = "chained" if ops.conv2d_chain_ok_geometry(B, 2 * H, 2 * W, dtype, pk(front), both) else "separate"
+    n, c_, lowp = len(c3.m), c3.cv1.conv.out_channels, dtype in (torch.bfloat16, torch.float16)
+    cv1, cv2 = [pk(b.cv1) for b in c3.m], [pk(b.cv2) for b in c3.m]
+    steps = _blocks(n)
+    if lowp and c_ not in (64, 128) and c3.chain and c3.chain_pairs:
+        if all(b.add for b in c3.m):
+            if all(ops.conv2d_chain_res_ok_geometry(B, H, W, dtype, cv2[j], cv1[j + 1]) for j in range(n - 1)):
+                steps = _res_chain(n)
+        else:
+            can = [ops.conv2d_chain_ok_geometry(B, H, W, dtype, cv2[j], cv1[j + 1]) for j in range(n - 1)] + [False]
+            steps = []
+            for j in range(n):
+                took = j > 0 and can[j - 1]
+                steps += [("block", j)] if not (took or can[j]) else ([] if took else [("cv1", j)]) + [("pair" if can[j] else "cv2", j)]
+            steps = tuple(steps)
+    return (how, False, steps)
+
+
+def test_c3_launch_plans_of_cfg3(monkeypatch):
+    """C3.launch_plan on a CPU-resident cfg3, every C3 at the geometry it sees: the front conv chained at 64 / 128 channels (rows 2, 7, 4, 9)
+    and run separately in front of the 512-wide pairs (14, 16); 64 / 128-channel Bottlenecks left to their own forward (the patch-resident
+    kernel); the shortcut chain in the 256-channel backbone C3s only from ops.CHAIN_RES_MIN_ROWS pixels; the shortcut-free pair chains at
+    256 channels (35, 42), nothing at 512 (22, 25, 45).  fp32 and training chain nothing; C3.chain / C3.chain_pairs switch the pair forms off
+    and leave the front chains alone."""
+    from msod_amd.models.common import C3
+    model = Model(configs.named_config("cfg3"))
+    assert sorted(i for i, m in enumerate(model.model) if isinstance(m, C3)) == sorted(C3_STRIDE)
+    bf16 = torch.bfloat16
+    table = {2: ("chained", False, _blocks(3)), 7: ("chained", False, _blocks(3)), 4: ("chained", False, _blocks(9)), 9: ("chained", False, _blocks(9)),
+             14: ("separate", False, _res_chain(9)), 16: ("separate", False, _res_chain(9)),
+             22: (None, False, _blocks(3)), 25: (None, False, _blocks(3)), 45: (None, False, _blocks(3)),
+             35: (None, False, PAIRS3), 42: (None, False, PAIRS3), 39: (None, False, _blocks(3))}
+    small = dict(table)
+    small[14] = small[16] = ("separate", False, _blocks(9))              # 2 * 12 * 16 pixels: below the size heuristic
+    assert _c3_plans(model, 64, 640, 640, bf16, _restated_plan) == table
+    assert _c3_plans(model, 2, 192, 256, bf16, _restated_plan) == small
+    monkeypatch.setattr(ops, "CHAIN_RES_MIN_ROWS", 0)
+    assert _c3_plans(model, 2, 192, 256, bf16, _restated_plan) == table
+    assert _c3_plans(model, 2, 192, 256, torch.float16, _restated_plan) == table
+    no_pairs = {i: (front, False, _blocks(len(model.model[i].m))) for i, (front, _, _) in table.items()}      # the front chains stay
+    for i, (front, split, steps) in _c3_plans(model, 64, 640, 640, torch.float32, _restated_plan).items():
+        assert (front, split, steps) == ("separate" if i in (2, 7, 4, 9, 14, 16) else None, False, _blocks(len(model.model[i].m))), i
+    monkeypatch.setattr(C3, "chain_pairs", False)                        # what bench.py --no-pair-chain does
+    assert _c3_plans(model, 64, 640, 640, bf16, _restated_plan) == no_pairs
+    monkeypatch.setattr(C3, "chain_pairs", True)
+    model.chain_convs = False                                            # C3.chain on every instance (and no conv is handed over any more)
+    assert _c3_plans(model, 64, 640, 640, bf16, _restated_plan) == no_pairs
+    model.chain_convs = True
+    model.chain_pairs = False
+    assert _c3_plans(model, 64, 640, 640, bf16) == no_pairs
+    model.chain_pairs = True
+    assert _c3_plans(model, 64, 640, 640, bf16) == table
+    model.train()
+    for i, (front, split, steps) in _c3_plans(model, 64, 640, 640, bf16).items():
+        assert (front, split, steps) == ("separate" if i in (2, 7, 4, 9, 14, 16) else None, True, _blocks(len(model.model[i].m))), i
+
+
+def test_c3_launch_plan_cache(monkeypatch):
+    """One cache per C3, keyed on everything the decision reads: a repeated request asks ``cft_conv2d_chain_ok`` nothing and returns the
+    same plan; another CHAIN_RES_MIN_ROWS, chain, chain_pairs (instance or class), training, dtype, B or source ld is decided afresh;
+    ``invalidate_packed`` drops the cache."""
+    from msod_amd.models.common import C3, invalidate_packed
+    model = Model(configs.named_config("cfg3"))
+    c3, front = model.model[14], model.model[13]
+    asked, real = [], ops.conv2d_chain_ok_geometry
+    monkeypatch.setattr(ops, "conv2d_chain_ok_geometry", lambda *a, **k: asked.append(a[:3]) or real(*a, **k))
+
+    def fresh(*args, **kw):
+        """The request makes a new cache entry, and asks the library unless it is the training form."""
+        n, entries = len(asked), len(c3.__dict__.get("_plan_cache", {}))
+        plan = c3.launch_plan(*args, **kw)
+        new, n1 = len(c3._plan_cache) - entries, len(asked)
+        assert new == 1 or (new == 0 and n1 == n)
+        assert c3.launch_plan(*args, **kw) is plan and len(asked) == n1 and len(c3._plan_cache) == entries + new
+        return new == 1 and (n1 > n or plan.split), plan
+    base = (64, 80, 80, torch.bfloat16, front)
+    decided, plan = fresh(*base)
+    assert decided and len(asked) == 1 + 8 and plan.steps == _res_chain(9)          # the front pair, then 8 Bottleneck pairs
+    assert fresh(*base) == (False, plan)
+    monkeypatch.setattr(ops, "CHAIN_RES_MIN_ROWS", 64 * 40 * 40 + 1)
+    assert fresh(*base) == (True, plan._replace(steps=_blocks(9)))
+    monkeypatch.setattr(ops, "CHAIN_RES_MIN_ROWS", 0)
+    assert fresh(*base)[0] and fresh(64, 80, 80, torch.float32, front)[0] and fresh(8, 80, 80, torch.bfloat16, front)[0]
+    assert fresh(64, 80, 80, torch.bfloat16, front, ld_in=512)[0] and fresh(64, 80, 80, torch.bfloat16, front, 256)[0]
+    assert fresh(64, 40, 40, torch.bfloat16)[0]                                     # no conv handed over: the grid is cv1|cv2's own
+    c3.chain = False
+    assert fresh(*base) == (True, plan._replace(steps=_blocks(9)))
+    c3.chain = True
+    c3.chain_pairs = False
+    assert fresh(*base) == (True, plan._replace(steps=_blocks(9)))
+    del c3.chain_pairs
+    monkeypatch.setattr(C3, "chain_pairs", False)
+    assert c3.launch_plan(*base).steps == _blocks(9)                                # (the entry of the instance switch: the key holds the value)
+    monkeypatch.setattr(C3, "chain_pairs", True)
+    assert fresh(*base) == (False, plan)
+    c3.train()
+    assert fresh(*base) == (True, plan._replace(split=True, steps=_blocks(9)))
+    c3.eval()
+    for b in range(1, 20):                                                          # bounded
+        c3.launch_plan(b, 40, 40, torch.bfloat16)
+    assert len(c3._plan_cache) <= 17
+    invalidate_packed(model)
+    assert "_plan_cache" not in c3.__dict__ and fresh(*base) == (True, plan)
+
+
+# ---- the CFT residual stream (_ResidualStream) -------------------------------------------------------------------------------------
+def _traced_gpt(monkeypatch, rows, n_layer=1, p=0.1, train=False, splitk=True):
+    """Names of the ops calls of one ``GPT(d_model=256, block_exp=4)`` forward on ``rows`` token rows; the kernels are replaced by recorders that
+    return empty tensors which say they live on the GPU."""
+    from msod_amd.models.common import GPT
+    calls = []
+
+    def gpu(*shape, dtype=torch.bfloat16):
+        return torch.empty(shape, dtype=dtype, device="meta").as_subclass(_OnGpu)
+
+    def linear(x, pk, act=ops.ACT_NONE, residual=None, out=None, out_dtype=None):
+        assert (residual is None and out is None) or (residual is out and out.dtype == out_dtype == torch.float32)
+        calls.append(f"linear{pk.n}" + ("+gelu" if act == ops.ACT_GELU else "") + ("+x" if out is not None else "") + (":f32" if out is None and out_dtype == torch.float32 else ""))
+        return out if out is not None else gpu(x.shape[0], pk.n, dtype=out_dtype or x.dtype)
+
+    def norm(name):
+        def fn(x, *a):
+            out_dtype = a[-2]
+            calls.append(name + (f"[{a[0].shape[0]}]" if name == "layernorm_reduce" else "") + (":f32" if out_dtype == torch.float32 else ""))
+            return gpu(*x.shape, dtype=out_dtype)
+        return fn
+    monkeypatch.setattr(ops, "gpt_tokenize", lambda rgb, ir, pos, grid: gpu(rgb.shape[0], 128, rgb.shape[1], dtype=torch.float32))
+    monkeypatch.setattr(ops, "linear", linear)
+    monkeypatch.setattr(ops, "layernorm", norm("layernorm"))
+    monkeypatch.setattr(ops, "layernorm_reduce", norm("layernorm_reduce"))
+    monkeypatch.setattr(ops, "attention", lambda qkv, B, h, dk, dkp, pdrop, T: calls.append(f"attention(p={pdrop:g})") or gpu(qkv.shape[0], h * dkp))
+    monkeypatch.setattr(ops, "linear_splitk", lambda x, pk, s: calls.append(f"linear_splitk{pk.n}[{s}]") or gpu(s, x.shape[0], pk.n, dtype=torch.float32))
+    monkeypatch.setattr(ops, "dropout_", lambda x, p_: calls.append(f"dropout(p={p_:g})"))
+    monkeypatch.setattr(ops, "add_rows_", lambda x, y: calls.append("add_rows"))
+    gpt = GPT(256, h=8, block_exp=4, n_layer=n_layer, embd_pdrop=p, attn_pdrop=p, resid_pdrop=p).train(train)
+    for blk in gpt.trans_blocks:
+        blk.splitk = splitk
+    B = rows // 128
+    gpt((gpu(B, 256, 16, 16), gpu(B, 256, 16, 16)))
+    return calls
+
+
+def test_cft_residual_stream_call_sequences(monkeypatch):
+    """One transformer block + ln_f (d = 256, block_exp 4; ops.splitk_choice: out_proj 1, fc2 4 at 1024 rows, see test_splitk_choice_rule):
+    which GEMM form adds to the residual stream and which LayerNorm form follows it, in inference with and without split-K and in training
+    with and without dropout; pending partial sums reach the next block's ln_input and, from the last block, ln_f."""
+    head = ["layernorm", "linear768", "attention(p=0)", "linear256+x", "layernorm", "linear1024+gelu"]
+    in_place = head + ["linear256+x", "layernorm:f32"]
+    assert _traced_gpt(monkeypatch, 1024) == head + ["linear_splitk256[4]", "layernorm_reduce[4]:f32"]
+    assert _traced_gpt(monkeypatch, 8192) == in_place
+    assert _traced_gpt(monkeypatch, 1024, splitk=False) == in_place
+    assert _traced_gpt(monkeypatch, 1024, train=True, p=0.0) == ["dropout(p=0)"] + in_place
+    drop = ["linear256:f32", "dropout(p=0.1)", "add_rows"]
+    assert _traced_gpt(monkeypatch, 1024, train=True) == (["dropout(p=0.1)", "layernorm", "linear768", "attention(p=0.1)"] + drop
+                                                          + ["layernorm", "linear1024+gelu"] + drop + ["layernorm:f32"])
+    assert _traced_gpt(monkeypatch, 1024, n_layer=2) == (head + ["linear_splitk256[4]", "layernorm_reduce[4]"] + head[1:]
+                                                         + ["linear_splitk256[4]", "layernorm_reduce[4]:f32"])
 
 
 def test_executor_plans_reproduce_the_recorded_ones_and_follow_the_layer_list():
