@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bump with every change of a prototype below (history: csrc/runtime.hip).  The Python binding reads this line, the enums and
  * every prototype from this file: it is the only description of the ABI. */
-#define CFT_ABI_VERSION 17
+#define CFT_ABI_VERSION 18
 
 enum { CFT_BF16 = 0, CFT_F32 = 1, CFT_F16 = 2 };
 enum { CFT_ACT_NONE = 0, CFT_ACT_SILU = 1, CFT_ACT_GELU = 2 };
@@ -431,6 +431,70 @@ int cft_eval_confusion(const float* dets, const int* counts, int B, int max_det,
  * Slots r >= counts[b] are zero.  out must be 16-byte aligned.  One launch, no allocation, no synchronisation.
  */
 int cft_eval_export(const float* dets, const int* counts, int B, int max_det, const float* geom, int single_cls, float* out, void* stream);
+
+/*
+ * The device stage of detect_twostream.py between non_max_suppression and the files it writes (:129-153).  Both calls are
+ * asynchronous, allocate nothing and do not synchronise.
+ *
+ * cft_detect_boxes computes what the loop says about each detection slot of the cft_nms output, float32 with one rounding per
+ * operation in the reference's order.  out [B, max_det, 16], 32-bit words:
+ *    0..3  x1 y1 x2 y2 (int)  scale_coords + clip_coords, then .round() (:131; half to even)
+ *    4     cls (int)          int(cls), truncation toward zero (:147); -1 for a NaN
+ *    5     conf (int)         hundredths 0..100, the digits of f'{conf:.2f}' (:148): correctly rounded, ties to even on the float's
+ *                             exact binary value, computed in integers; values above 1 saturate at 100, negative ones and NaN give 0
+ *    6     valid (int)        1 for r < counts[b]
+ *    7     conf (float)       the confidence itself, what save_conf writes with %g (:142-144)
+ *    8..11 x1 y1 x2 y2 (int)  the save_one_box rectangle (utils/general.py:628-637): xyxy2xywh of the rounded box, the larger side for
+ *                             both when square != 0, wh * crop_gain + crop_pad, xywh2xyxy, .long() (toward zero), clip_coords;
+ *                             the crop is rows [y1, y2) and columns [x1, x2)
+ *    12..15 x y w h (float)   xyxy2xywh of the ROUNDED box / (w0, h0, w0, h0), the save_txt line (:141)
+ * Slots r >= counts[b] are zero.  hist [B, nc] int (overwritten): detections per class of each image, the "3 persons, 1 car" line
+ * (:134-136).  A class outside [0, nc) is not counted and ORs 1 into flag [1] (int, device).
+ *   dets [B, max_det, 6] / counts [B] : the cft_nms output;  geom [B, 5] : h0, w0, gain, padw, padh as for cft_eval_match
+ *   out must be 16-byte aligned; nc in [1, 32767]
+ */
+int cft_detect_boxes(const float* dets, const int* counts, int B, int max_det, const float* geom, int nc, float crop_gain, float crop_pad,
+                     int square, int* out, int* hist, int* flag, void* stream);
+
+/*
+ * cft_detect_render draws the boxes of a whole batch into the device copies of the original images, both streams, in place, in one
+ * launch (plot_one_box, utils/plots.py:67-81, as detect_twostream.py:139-151 calls it for reversed(det) on im0 and im0_).
+ * cv2's anti-aliased thick lines and Hershey font are not reproduced ("parity with cv2 unpinned"); the raster is defined here.
+ * For a valid slot with box (x1, y1, x2, y2), class c in [0, nc) and thickness t, all divisions integer, all ranges inclusive:
+ *   outline     a = t / 2; the pixels of [x1 - a, x2 + a] x [y1 - a, y2 + a] that are not inside
+ *               [x1 + t - a, x2 - t + a] x [y1 + t - a, y2 - t + a] take colour[c]; no anti-aliasing;
+ *   label       (flag labels) the string is name[c], followed by ' ' and d.dd from the hundredths word when flag conf is set; n = its
+ *               length, no label when n == 0; magnification m = max(1, (t + 1) / 3), glyph cell gw*m x gh*m;
+ *     background columns x1 .. x1 + n*gw*m, rows y1 - gh*m - 3 .. y1 take colour[c] (the corners of utils/plots.py:79-80);
+ *     text       character k occupies columns x1 + k*gw*m .. x1 + (k+1)*gw*m - 1, rows y1 - 1 - gh*m .. y1 - 2; pixel (px, py) of
+ *                it takes the text colour where atlas[code - 32][(py - top) / m][(px - left) / m] >= 128 (a code outside 32..127
+ *                draws as a space).
+ * Everything is clipped to the h0 x w0 image (x2 == w0 is legal after clip_coords).  Painter's order is the reference's: it draws
+ * reversed(det), outline, background, text, so a pixel ends as the covering slot with the LOWEST row index says, and within that
+ * slot text wins over background over outline.  The kernel finds exactly that per pixel; each covered pixel is written once, by one
+ * thread, uncovered pixels are neither read nor written: the image does not depend on scheduling.
+ *   desc_dev / desc_host : B rows of cft_render_desc_t, device copy (read by the kernel) and the same bytes on the host (read by the
+ *                          guards: pointers, strides, sizes are checked before the launch; nothing is launched on CFT_EINVAL).
+ *                          img_ir may be NULL (one stream only)
+ *   boxes [B, max_det, 16]: the cft_detect_boxes output (words 0..6 are read)
+ *   colors [nc, 3] uint8 in the images' channel order; text_color = c0 | c1 << 8 | c2 << 16
+ *   names [nc, name_ld] uint8 character codes, name_len [nc] int (clamped to [0, name_ld]); name_ld in [1, 32]
+ *   atlas [96, gh, gw] uint8 for the codes 32..127; gh, gw in [1, 64]; thickness in [1, 64]
+ */
+#define CFT_RENDER_DESC_BYTES 48
+#define CFT_RENDER_LABELS 1
+#define CFT_RENDER_CONF 2
+#define CFT_RENDER_MAX_NAME 32
+typedef struct {
+  unsigned char* img_rgb;         /* HWC uint8, pixels contiguous */
+  unsigned char* img_ir;          /* same size, or NULL */
+  long stride_rgb, stride_ir;     /* row strides in bytes, >= 3 * w0 */
+  int h0, w0;
+  int pad0, pad1;                 /* 0 */
+} cft_render_desc_t;
+int cft_detect_render(const void* desc_dev, const void* desc_host, int B, const int* boxes, int max_det, const unsigned char* colors, int nc,
+                      int text_color, int thickness, int flags, const unsigned char* names, const int* name_len, int name_ld,
+                      const unsigned char* atlas, int gh, int gw, void* stream);
 
 /*
  * ComputeLoss of the reference (utils/loss.py:88-216) and its gradient with respect to the head outputs.

@@ -707,7 +707,7 @@ class autoShape(nn.Module):
     shape = the largest scaled image rounded up to the stride, ``letterbox(auto=False)``, BHWC -> BCHW, / 255) with the letterbox on
     the device (``cft_letterbox_u8``) and the / 255 fused into Focus; post-processing :317-320 (``non_max_suppression`` =
     ``cft_nms``, ``scale_coords`` back to every original image).  Returns the list of per-image ``[n, 6]`` (xyxy, conf, cls)
-    tensors in ORIGINAL-image pixels (the reference wraps the same list in its plotting class ``Detections``, out of scope)."""
+    tensors in ORIGINAL-image pixels; with ``detections=True`` that list wrapped in ``Detections`` (below), as the reference returns it."""
     conf = 0.25
     iou = 0.45
     classes = None
@@ -739,7 +739,7 @@ class autoShape(nn.Module):
         return t.contiguous().to(device)
 
     @torch.no_grad()
-    def forward(self, rgb, ir, size=640, augment=False, profile=False):
+    def forward(self, rgb, ir, size=640, augment=False, profile=False, detections=False):
         from ..models.yolo_test import make_divisible
         from ..utils.datasets import letterbox
         from ..utils.general import non_max_suppression, scale_coords
@@ -769,6 +769,126 @@ class autoShape(nn.Module):
         y = non_max_suppression(y, conf_thres=self.conf, iou_thres=self.iou, classes=self.classes)
         for i in range(n):
             scale_coords(shape1, y[i][:, :4], shape0[i])
+        if detections:
+            files = [f"image{i}.jpg" for i in range(n)]
+            return Detections(rgbs, y, files, names=getattr(self, "names", None), shape=tuple(batch[:, :3].shape), imgs_ir=irs)
         return y
+
+
+class Detections:
+    """The reference's ``Detections`` (models/common.py:330-414) for two streams: ``imgs`` / ``imgs_ir`` are the original images as HWC
+    uint8 CUDA tensors (RGB), ``pred`` the per-image ``[n, 6]`` (xyxy, conf, cls) tensors in original-image pixels.  ``render`` draws
+    every box with its ``name conf`` label into both streams' images with one ``cft_detect_render`` launch (this project's raster,
+    include/cft_hip.h; boxes rounded and painted as detect_twostream.py does, the most confident on top) and returns them; ``save`` and
+    ``crop`` write files with PIL; ``show`` needs a display and raises."""
+
+    def __init__(self, imgs, pred, files, times=None, names=None, shape=None, imgs_ir=None):
+        from ..utils.general import xyxy2xywh
+        d = pred[0].device
+        gn = [torch.tensor([*[im.shape[i] for i in [1, 0, 1, 0]], 1., 1.], device=d) for im in imgs]
+        self.imgs = imgs
+        self.imgs_ir = imgs_ir
+        self.pred = pred
+        self.names = names
+        self.files = files
+        self.xyxy = pred
+        self.xywh = [xyxy2xywh(x) for x in pred]
+        self.xyxyn = [x / g for x, g in zip(self.xyxy, gn)]
+        self.xywhn = [x / g for x, g in zip(self.xywh, gn)]
+        self.n = len(self.pred)
+        self.t = tuple((times[i + 1] - times[i]) * 1000 / self.n for i in range(3)) if times is not None else (0.0, 0.0, 0.0)
+        self.s = shape
+        self._rendered = False
+
+    def _names(self):
+        nc = 1 + max([int(p[:, 5].max()) for p in self.pred if len(p)] or [0])
+        return list(self.names) if self.names is not None else [str(i) for i in range(nc)]
+
+    def _boxes(self):
+        """``cft_detect_boxes`` on the predictions (already in original-image pixels: gain 1, no padding)."""
+        from ..ops import detect_boxes
+        from ..utils.metrics import _pack_dets, _to_device
+        d = self.pred[0].device
+        dets, counts = _pack_dets(list(self.pred), None, d)
+        geom = torch.tensor([[im.shape[0], im.shape[1], 1.0, 0.0, 0.0] for im in self.imgs], dtype=torch.float32)
+        return detect_boxes(dets.contiguous(), counts, _to_device(geom, d), len(self._names()))
+
+    def _strings(self):
+        out = []
+        for i, (im, pred) in enumerate(zip(self.imgs, self.pred)):
+            s = f'image {i + 1}/{len(self.pred)}: {im.shape[0]}x{im.shape[1]} '
+            for c in pred[:, -1].unique().tolist():
+                n = int((pred[:, -1] == c).sum())
+                s += f"{n} {self._names()[int(c)]}{'s' * (n > 1)}, "
+            out.append(s.rstrip(', '))
+        return out
+
+    def print(self):
+        for s in self._strings():
+            print(s)
+        print(f'Speed: %.1fms pre-process, %.1fms inference, %.1fms NMS per image at shape {tuple(self.s)}' % self.t)
+
+    def show(self):
+        raise NotImplementedError("Detections.show needs a display; use render() or save()")
+
+    def render(self, line_thickness=3, atlas=None):
+        from ..utils.plots import BoxRenderer
+        if not self._rendered:
+            boxes, _, _ = self._boxes()
+            r = BoxRenderer(self._names(), boxes.device, line_thickness, hide_labels=False, hide_conf=False, atlas=atlas)
+            r(boxes, self.imgs, self.imgs_ir)
+            self._rendered = True
+        return self.imgs if self.imgs_ir is None else (self.imgs, self.imgs_ir)
+
+    def save(self, save_dir='runs/hub/exp'):
+        from PIL import Image
+        from ..utils.general import increment_path
+        save_dir = increment_path(save_dir, exist_ok=save_dir != 'runs/hub/exp', mkdir=True)
+        self.render()
+        for i, f in enumerate(self.files):
+            Image.fromarray(self.imgs[i].cpu().numpy()).save(save_dir / f)
+            if self.imgs_ir is not None:
+                stem, _, ext = str(f).rpartition('.')
+                Image.fromarray(self.imgs_ir[i].cpu().numpy()).save(save_dir / f'{stem}_ir.{ext}')
+            print(f"{'Saved' * (i == 0)} {f}", end=',' if i < self.n - 1 else f' to {save_dir}\n')
+
+    def crop(self, save_dir='runs/hub/exp'):
+        """One file per detection under ``save_dir/crops/<class>/``: the reference's rectangle of the UNROUNDED box (``crop_rectangle``),
+        cut from the RGB original on the host.  Crop before ``render`` / ``save``: they draw into the images."""
+        from ..utils.general import crop_rectangle, increment_path, save_one_box
+        if self._rendered:
+            raise RuntimeError("Detections.crop: the images have been drawn into; crop before render() / save()")
+        save_dir = increment_path(save_dir, exist_ok=save_dir != 'runs/hub/exp', mkdir=True)
+        names = self._names()
+        for i, im in enumerate(self.imgs):
+            host = im.cpu().numpy()
+            for *box, conf, cls in self.pred[i].tolist():
+                save_one_box(box, host, file=save_dir / 'crops' / names[int(cls)] / self.files[i], rect=crop_rectangle(box, host.shape))
+        print(f'Saved results to {save_dir}\n')
+
+    def pandas(self):
+        """A copy whose xyxy / xyxyn / xywh / xywhn are lists of pandas DataFrames with the reference's column names."""
+        import pandas as pd
+        from copy import copy
+        new = copy(self)
+        ca = 'xmin', 'ymin', 'xmax', 'ymax', 'confidence', 'class', 'name'
+        cb = 'xcenter', 'ycenter', 'width', 'height', 'confidence', 'class', 'name'
+        names = self._names()
+        for k, c in zip(['xyxy', 'xyxyn', 'xywh', 'xywhn'], [ca, ca, cb, cb]):
+            a = [[x[:5] + [int(x[5]), names[int(x[5])]] for x in x.tolist()] for x in getattr(self, k)]
+            setattr(new, k, [pd.DataFrame(x, columns=c) for x in a])
+        return new
+
+    def tolist(self):
+        """One Detections per image, its list attributes replaced by that image's element."""
+        x = [Detections([self.imgs[i]], [self.pred[i]], [self.files[i]], names=self.names, shape=self.s,
+                        imgs_ir=None if self.imgs_ir is None else [self.imgs_ir[i]]) for i in range(self.n)]
+        for d in x:
+            for k in ['imgs', 'pred', 'xyxy', 'xyxyn', 'xywh', 'xywhn']:
+                setattr(d, k, getattr(d, k)[0])
+        return x
+
+    def __len__(self):
+        return self.n
 
 Classify = _outside("Classify", "models/common.py:417-427")

@@ -723,6 +723,69 @@ def pair_batch_u8(desc_dev, desc_host, out, color=114):
     return out
 
 
+BOX_WORDS = 16        # 32-bit words per detection slot of cft_detect_boxes (include/cft_hip.h)
+
+
+def detect_boxes(dets, counts, geom, nc, crop_gain=1.02, crop_pad=10, square=False, flag=None):
+    """cft_detect_boxes on the batched_nms output: ``(boxes int32 [B, max_det, 16], hist int32 [B, nc], flag int32 [1])``, all on the
+    device; the four float words 12..15 of a slot are read with ``boxes[..., 12:].view(torch.float32)``.  ``flag`` is ORed into."""
+    for t in (dets, counts, geom):
+        _require_cuda(t, "detect_boxes")
+    if dets.dtype != torch.float32 or dets.dim() != 3 or dets.shape[2] != 6 or not dets.is_contiguous() or dets.shape[0] == 0 or dets.shape[1] == 0:
+        raise ValueError(f"detect_boxes: dets must be a contiguous float32 [B, max_det, 6] tensor, got {dets.dtype} {tuple(dets.shape)}")
+    B, max_det = dets.shape[0], dets.shape[1]
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or not counts.is_contiguous():
+        raise ValueError(f"detect_boxes: counts must be a contiguous int32 [{B}] tensor")
+    if geom.dtype != torch.float32 or tuple(geom.shape) != (B, 5) or not geom.is_contiguous():
+        raise ValueError(f"detect_boxes: geom must be a contiguous float32 [{B}, 5] tensor")
+    boxes = torch.empty((B, max_det, BOX_WORDS), dtype=torch.int32, device=dets.device)
+    hist = torch.empty((B, int(nc)), dtype=torch.int32, device=dets.device)
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=dets.device)
+    st = _lib.load().cft_detect_boxes(dets.data_ptr(), counts.data_ptr(), B, max_det, geom.data_ptr(), int(nc), float(crop_gain), float(crop_pad),
+                                      int(bool(square)), boxes.data_ptr(), hist.data_ptr(), flag.data_ptr(), _stream())
+    _lib.check(st, "cft_detect_boxes")
+    return boxes, hist, flag
+
+
+def detect_render(desc_dev, desc_host, boxes, colors, text_color, thickness, flags, names=None, name_len=None, atlas=None):
+    """cft_detect_render: draws the slots of ``boxes`` [B, max_det, 16] into the images of the table (``desc_dev`` [B, 48] uint8 on the
+    device, ``desc_host`` the same bytes on the host), in place.  ``colors`` uint8 [nc, 3], ``names`` uint8 [nc, L], ``name_len`` int32
+    [nc], ``atlas`` uint8 [96, gh, gw], all on the device; ``text_color`` three bytes."""
+    nb = _lib._consts["CFT_RENDER_DESC_BYTES"]
+    B = boxes.shape[0]
+    for t, what in ((desc_dev, "desc_dev"), (desc_host, "desc_host")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (B, nb) or not t.is_contiguous():
+            raise ValueError(f"detect_render: {what} must be a contiguous uint8 [{B}, {nb}] tensor")
+    if desc_host.is_cuda:
+        raise ValueError("detect_render: desc_host must be a host tensor")
+    if boxes.dtype != torch.int32 or boxes.dim() != 3 or boxes.shape[2] != BOX_WORDS or not boxes.is_contiguous():
+        raise ValueError("detect_render: boxes must be the contiguous int32 [B, max_det, 16] output of detect_boxes")
+    if colors.dtype != torch.uint8 or colors.dim() != 2 or colors.shape[1] != 3 or not colors.is_contiguous():
+        raise ValueError("detect_render: colors must be a contiguous uint8 [nc, 3] tensor")
+    nc = colors.shape[0]
+    dev = [desc_dev, boxes, colors]
+    L = gh = gw = 0
+    if flags & _lib._consts["CFT_RENDER_LABELS"]:
+        if names is None or name_len is None or atlas is None:
+            raise ValueError("detect_render: labels need names, name_len and atlas")
+        if names.dtype != torch.uint8 or names.dim() != 2 or names.shape[0] != nc or not names.is_contiguous():
+            raise ValueError(f"detect_render: names must be a contiguous uint8 [{nc}, L] tensor")
+        if name_len.dtype != torch.int32 or tuple(name_len.shape) != (nc,) or not name_len.is_contiguous():
+            raise ValueError(f"detect_render: name_len must be a contiguous int32 [{nc}] tensor")
+        if atlas.dtype != torch.uint8 or atlas.dim() != 3 or atlas.shape[0] != 96 or not atlas.is_contiguous():
+            raise ValueError("detect_render: atlas must be a contiguous uint8 [96, gh, gw] tensor")
+        L, gh, gw = names.shape[1], atlas.shape[1], atlas.shape[2]
+        dev += [names, name_len, atlas]
+    for t in dev:
+        _require_cuda(t, "detect_render")
+    tc = int(text_color[0]) | int(text_color[1]) << 8 | int(text_color[2]) << 16
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    st = _lib.load().cft_detect_render(desc_dev.data_ptr(), desc_host.data_ptr(), B, boxes.data_ptr(), boxes.shape[1], colors.data_ptr(), nc, tc,
+                                       int(thickness), int(flags), ptr(names), ptr(name_len), L, ptr(atlas), gh, gw, _stream())
+    _lib.check(st, "cft_detect_render")
+
+
 # ------------------------------------------------------------------------------ training-mode forward
 _dropout_state = {"seed": 0x5EED, "calls": 0}
 

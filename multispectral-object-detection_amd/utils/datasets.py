@@ -569,3 +569,191 @@ def create_dataloader_rgb_ir(path1, path2, imgsz, batch_size, stride, opt, hyp=N
                                             image_weights=image_weights,
                                             prefix=prefix)
     return PairLoader(dataset, batch_size, workers=workers, rank=rank, world_size=world_size), dataset
+
+
+# ------------------------------------------------------------------------------ inference loaders (detect_twostream.py)
+# LoadImages of the reference (utils/datasets.py:299-376) and the zip of two of them that detect_twostream.py:66 iterates, with the
+# letterbox (auto=True, scale-up allowed, :362) on the device.  Files are decoded with PIL, so the originals are RGB (cv2.imread gives
+# the same pixels in BGR order); video files need cv2 and raise.
+vid_formats = ['mov', 'avi', 'mp4', 'mpg', 'mpeg', 'm4v', 'wmv', 'mkv']  # acceptable video suffixes (reference :34)
+
+
+def _letterbox_chw_rgb(img, out, rh, rw, top, left):
+    """RGB HWC uint8 CUDA image -> the CHW RGB letterbox ``out`` [3, H, W] (cft_letterbox_u8 without the channel flip)."""
+    st = _lib.load().cft_letterbox_u8(img.data_ptr(), img.shape[0], img.shape[1], img.stride(0), out.data_ptr(), out.shape[1], out.shape[2],
+                                      out.stride(1), out.stride(2), out.stride(0), 0, rh, rw, top, left, 114, 114, 114, _stream())
+    _lib.check(st, "cft_letterbox_u8")
+
+
+def _inference_geometry(h0, w0, img_size, stride):
+    """(H, W, rh, rw, top, left) of LoadImages' letterbox (reference :362: auto=True, scaleup=True)."""
+    (rw, rh), _, _, (top, bottom, left, right) = letterbox_geometry((h0, w0), img_size, auto=True, scaleup=True, stride=stride)
+    return rh + top + bottom, rw + left + right, rh, rw, top, left
+
+
+class LoadImages:  # for inference
+    """The reference's ``LoadImages`` (utils/datasets.py:299-376): a glob, a directory or one file; iterating yields
+    ``(path, img, im0, None)`` with ``img`` the CHW RGB uint8 CUDA letterbox and ``im0`` the HWC RGB uint8 CUDA original."""
+
+    def __init__(self, path, img_size=640, stride=32, device=None):
+        p = str(Path(path).absolute())
+        if '*' in p:
+            files = sorted(glob.glob(p, recursive=True))
+        elif os.path.isdir(p):
+            files = sorted(glob.glob(os.path.join(p, '*.*')))
+        elif os.path.isfile(p):
+            files = [p]
+        else:
+            raise Exception(f'ERROR: {p} does not exist')
+
+        images = [x for x in files if x.split('.')[-1].lower() in img_formats]
+        videos = [x for x in files if x.split('.')[-1].lower() in vid_formats]
+        if videos:
+            raise NotImplementedError(f'LoadImages: video files need cv2.VideoCapture, which this package does not use ({videos[0]})')
+        self.img_size = img_size
+        self.stride = stride
+        self.files = images
+        self.nf = len(images)
+        self.video_flag = [False] * self.nf
+        self.mode = 'image'
+        self.cap = None
+        self.device = device
+        assert self.nf > 0, f'No images or videos found in {p}. ' \
+                            f'Supported formats are:\nimages: {img_formats}\nvideos: {vid_formats}'
+
+    def __iter__(self):
+        self.count = 0
+        return self
+
+    def __next__(self):
+        if self.count == self.nf:
+            raise StopIteration
+        path = self.files[self.count]
+        self.count += 1
+        img0 = torch.from_numpy(decode_image(path)).to(torch.device(self.device if self.device is not None else "cuda"))
+        H, W, rh, rw, top, left = _inference_geometry(img0.shape[0], img0.shape[1], self.img_size, self.stride)
+        img = torch.empty((3, H, W), dtype=torch.uint8, device=img0.device)
+        _letterbox_chw_rgb(img0, img, rh, rw, top, left)
+        return path, img, img0, self.cap
+
+    def __len__(self):
+        return self.nf
+
+
+def image_size(path):
+    """(h0, w0) of an image file from its header, as ``decode_image`` will decode it."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size[1], im.size[0]
+
+
+class LoadImagePairs:
+    """Two ``LoadImages`` lists zipped as detect_twostream.py:66 zips them, in batches: consecutive pairs of the same original size
+    (up to ``batch_size``) form one uint8 ``[B, 6, H, W]`` batch.  Iterating yields ``(paths, img6, originals, shapes)``: ``paths`` a list
+    of (rgb path, ir path), ``originals`` a list of (rgb, ir) HWC RGB uint8 CUDA tensors (kept for drawing and cropping), ``shapes`` a list
+    of ``((h0, w0), None)`` as ``utils.metrics.geometry`` takes them; ``host_originals`` holds the decoded arrays of the batch just yielded.  A batch is one cft_pair_batch_u8 launch (CFT_PAIR_LINEAR, or
+    CFT_PAIR_COPY at ratio 1) where that kernel's guards admit it - an enlarging letterbox - else two cft_letterbox_u8 launches per pair.
+    The next batch is decoded on at most 16 threads and uploaded on a side stream while the current one is in use."""
+
+    def __init__(self, source1, source2, img_size=640, stride=32, batch_size=1, workers=8, device=None):
+        self.rgb = LoadImages(source1, img_size, stride)
+        self.ir = LoadImages(source2, img_size, stride)
+        self.img_size, self.stride = img_size, stride
+        self.batch_size = max(1, int(batch_size))
+        self.workers = max(1, min(int(workers), MAX_DECODE_THREADS))
+        self.device = torch.device(device if device is not None else "cuda")
+        self.mode = 'image'
+        self.pairs = list(zip(self.rgb.files, self.ir.files))       # zip stops at the shorter list, as the reference's loop does
+        self.shapes = []
+        for a, b in self.pairs:
+            sa, sb = image_size(a), image_size(b)
+            if sa != sb:
+                raise ValueError(f'LoadImagePairs: {a} is {sa[1]}x{sa[0]} but {b} is {sb[1]}x{sb[0]}: a pair must have one size')
+            self.shapes.append(sa)
+        self.batches = []                                          # lists of consecutive pair indices of one original size
+        for i, s in enumerate(self.shapes):
+            if self.batches and len(self.batches[-1]) < self.batch_size and self.shapes[self.batches[-1][0]] == s:
+                self.batches[-1].append(i)
+            else:
+                self.batches.append([i])
+        self._side = None
+        self.host_originals = None
+
+    def __len__(self):
+        return len(self.batches)
+
+    def batch_mode(self, indices):
+        """(resize mode or None, (H, W, rh, rw, top, left)) of a batch: None = the per-pair letterbox path."""
+        h0, w0 = self.shapes[indices[0]]
+        g = _inference_geometry(h0, w0, self.img_size, self.stride)
+        H, W, rh, rw = g[:4]
+        if W % 4:
+            return None, g
+        if (rh, rw) == (h0, w0):
+            return PAIR_COPY, g
+        if rh >= h0 and rw >= w0:
+            return PAIR_LINEAR, g
+        return None, g
+
+    def _load(self, i):
+        rgb, ir = decode_image(self.pairs[i][0]), decode_image(self.pairs[i][1])
+        for im, f in zip((rgb, ir), self.pairs[i]):
+            if im.shape[:2] != self.shapes[i]:
+                raise ValueError(f'{f}: decoded to {im.shape[1]}x{im.shape[0]}, its header says {self.shapes[i][1]}x{self.shapes[i][0]}')
+        return rgb, ir
+
+    def _stage(self, indices, pool):
+        """Decode and upload one batch on the side stream: (originals, device table or None, host table, event)."""
+        decoded = list(pool.map(self._load, indices))
+        nbytes = _align16(decoded[0][0].nbytes)
+        mode, (H, W, rh, rw, top, left) = self.batch_mode(indices)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            pinned = torch.empty(2 * nbytes * len(indices), dtype=torch.uint8).pin_memory()
+            host = pinned.numpy()
+            for k, (rgb, ir) in enumerate(decoded):
+                host[2 * k * nbytes:2 * k * nbytes + rgb.nbytes] = rgb.reshape(-1)
+                host[(2 * k + 1) * nbytes:(2 * k + 1) * nbytes + ir.nbytes] = ir.reshape(-1)
+            staged = pinned.to(self.device, non_blocking=True)
+            h0, w0 = self.shapes[indices[0]]
+            originals = [tuple(staged[(2 * k + s) * nbytes:(2 * k + s) * nbytes + h0 * w0 * 3].view(h0, w0, 3) for s in (0, 1))
+                         for k in range(len(indices))]
+            desc_host = desc_dev = None
+            if mode is not None:
+                desc = np.zeros(len(indices), dtype=PAIR_DESC)
+                for row in desc:
+                    row["h0"], row["w0"], row["h"], row["w"], row["top"], row["left"], row["mode"], row["flip"] = h0, w0, rh, rw, top, left, mode, 0
+                _fill_sources(desc, originals)
+                desc_host = torch.from_numpy(desc.view(np.uint8).reshape(len(indices), -1)).pin_memory()
+                desc_dev = desc_host.to(self.device, non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return indices, originals, staged, desc_host, desc_dev, ready, decoded
+
+    def _assemble(self, indices, originals, staged, desc_host, desc_dev, ready, decoded):
+        from ..ops import pair_batch_u8
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ready)
+        staged.record_stream(cur)                            # allocated on the side stream, read on this one
+        _, (H, W, rh, rw, top, left) = self.batch_mode(indices)
+        out = torch.empty((len(indices), 6, H, W), dtype=torch.uint8, device=self.device)
+        if desc_dev is not None:
+            desc_dev.record_stream(cur)
+            pair_batch_u8(desc_dev, desc_host, out, 114)
+        else:
+            for k, (rgb, ir) in enumerate(originals):
+                _letterbox_chw_rgb(rgb, out[k, :3], rh, rw, top, left)
+                _letterbox_chw_rgb(ir, out[k, 3:], rh, rw, top, left)
+        self.host_originals = decoded                        # the same pixels on the host, (rgb, ir) numpy arrays of the batch just yielded
+        paths = [self.pairs[i] for i in indices]
+        return paths, out, originals, [(self.shapes[i], None) for i in indices]
+
+    def __iter__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
+            nxt = stager.submit(self._stage, self.batches[0], pool) if self.batches else None
+            for k in range(len(self.batches)):
+                staged = nxt.result()
+                nxt = stager.submit(self._stage, self.batches[k + 1], pool) if k + 1 < len(self.batches) else None
+                yield self._assemble(*staged)

@@ -2,6 +2,10 @@
 (`test.py:129`, `detect_twostream.py:86`): `non_max_suppression` of the reference's
 `utils/general.py:455-543`, as ONE batched HIP kernel instead of a Python loop over images around
 `torchvision.ops.nms`."""
+import glob
+import re
+from pathlib import Path
+
 import torch
 
 from .. import _lib
@@ -127,3 +131,48 @@ def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None):
     coords[:, :4] /= gain
     clip_coords(coords, img0_shape)
     return coords
+
+
+def increment_path(path, exist_ok=False, sep='', mkdir=False):
+    """Increment file or directory path, i.e. runs/exp --> runs/exp{sep}2, runs/exp{sep}3, ... (reference utils/general.py:641-655).
+    The reference searches each similar path's WHOLE string for ``stem(\\d+)``, so a parent directory that happens to contain the stem
+    followed by digits (``.../e22a791/crops/a.jpg``) sets the number; here only the last path component is matched, literally."""
+    path = Path(path)
+    if path.exists() and not exist_ok:
+        suffix, base = path.suffix, path.with_suffix('')
+        pattern = re.compile(re.escape(base.stem) + re.escape(sep) + r"(\d+)")
+        taken = [int(m.group(1)) for m in (pattern.match(Path(d).name) for d in glob.glob(f"{base}{sep}*")) if m]
+        path = Path(f"{base}{sep}{max(taken) + 1 if taken else 2}{suffix}")
+    folder = path if path.suffix == '' else path.parent
+    if mkdir and not folder.exists():
+        folder.mkdir(parents=True, exist_ok=True)
+    return path
+
+
+def crop_rectangle(xyxy, im_shape, gain=1.02, pad=10, square=False):
+    """The rectangle ``save_one_box`` cuts (reference utils/general.py:630-636) for one box, float32 on the host op for op:
+    (x1, y1, x2, y2) integers, the crop is rows [y1, y2) and columns [x1, x2).  ``cft_detect_boxes`` computes the same per slot."""
+    xyxy = torch.tensor([float(v) for v in xyxy], dtype=torch.float32).view(-1, 4)
+    b = xyxy2xywh(xyxy)
+    if square:
+        b[:, 2:] = b[:, 2:].max(1)[0].unsqueeze(1)
+    b[:, 2:] = b[:, 2:] * gain + pad
+    xyxy = xywh2xyxy(b).long()
+    clip_coords(xyxy, im_shape)
+    return tuple(int(v) for v in xyxy[0])
+
+
+def save_one_box(xyxy, im, file='image.jpg', gain=1.02, pad=10, square=False, BGR=False, rect=None):
+    """Save an image crop as {file} with crop size multiplied by {gain} and padded by {pad} pixels (reference utils/general.py:628-638).
+    ``im`` is the undrawn original on the host (HWC uint8 numpy array); ``rect`` = words 8..11 of the box's slot of
+    ``cft_detect_boxes`` when the caller has the kernel's output, else the reference's arithmetic runs here on the lone box.  The file
+    is written with PIL, which takes RGB: ``BGR=True`` says ``im`` is in cv2's order.  Returns the path written, None for an empty crop
+    (cv2.imwrite raises on one)."""
+    from PIL import Image
+    x1, y1, x2, y2 = (int(v) for v in rect) if rect is not None else crop_rectangle(xyxy, im.shape, gain, pad, square)
+    crop = im[y1:y2, x1:x2]
+    path = increment_path(Path(file).with_suffix('.jpg'), mkdir=True)       # (the reference increments before it sets the suffix: x.png would overwrite x.jpg)
+    if crop.shape[0] == 0 or crop.shape[1] == 0:
+        return None
+    Image.fromarray(crop[..., ::-1].copy() if BGR else crop).save(str(path))
+    return path
