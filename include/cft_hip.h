@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bump with every change of a prototype below (history: csrc/runtime.hip).  The Python binding reads this line, the enums and
  * every prototype from this file: it is the only description of the ABI. */
-#define CFT_ABI_VERSION 18
+#define CFT_ABI_VERSION 19
 
 enum { CFT_BF16 = 0, CFT_F32 = 1, CFT_F16 = 2 };
 enum { CFT_ACT_NONE = 0, CFT_ACT_SILU = 1, CFT_ACT_GELU = 2 };
@@ -554,6 +554,51 @@ int cft_anchor_kmeans(const double* obs, long n, int k, const int* idx, int iter
 int cft_anchor_evolve_workspace_bytes(int gen, long* bytes);
 int cft_anchor_evolve(const float* wh, long n, int na, float thr, const double* v, int gen, double* k, float* f, int* flags, float* fg,
                       void* workspace, long workspace_bytes, void* stream);
+
+/*
+ * The second half of a training step (train.py:560-563 `optim.SGD(..., nesterov=True)` + the two `add_param_group`s, :769
+ * `scaler.step(optimizer)`, :773 `ema.update(model)`; utils/torch_utils.py:289-299 `ModelEMA.update`): ONE launch each over
+ * every tensor, whatever their number.  fp32 only; plain loads and stores, no atomics, no LDS: every element is read and written by
+ * exactly one thread, so the result is the same run to run.
+ *
+ * The tensors are described by a table that the caller builds once and keeps in device memory (`table_dev`, read by the kernel)
+ * and, byte for byte, in host memory (`table_host`, read by the guards: every row is checked before the launch and nothing is
+ * launched on CFT_EINVAL).  The table is nseg segment rows followed directly by nwork work rows:
+ *   segment: one tensor.  n elements (may be 0); every pointer a multiple of 4.
+ *   work   : cft_optim_work_t {seg, 0, start}: elements [start, min(start + chunk, n)) of segment seg.  The work rows list the
+ *            chunks of segment 0 in order, then those of segment 1, ... (a segment of n elements has ceil(n / chunk) rows):
+ *            the canonical cut, which the guards verify, so no element is covered twice.
+ * chunk: elements per work row, a multiple of 1024 in [1024, 2^20] (CFT_OPTIM_CHUNK is what the Python side uses).  One workgroup
+ * of 256 threads takes a work row at a time (grid-stride, at most max_blocks workgroups; 0 = CFT_OPTIM_MAX_BLOCKS).  A full chunk
+ * whose pointers are all multiples of 16 moves as 16-byte words, anything else (tails, views at an odd storage offset) as dwords.
+ *
+ * cft_sgd_step: torch.optim.SGD with dampening = 0 and maximize = False.  hyper_host: HOST float [ngroups][4] = lr, momentum,
+ * weight_decay, nesterov (0 / 1) of each param group, 1 <= ngroups <= CFT_OPTIM_MAX_GROUPS; it is copied into the kernel arguments
+ * (changing it between calls costs no device copy).  grad_scale / found_inf: DEVICE float [1] each or NULL, as torch.amp.GradScaler
+ * hands them to an optimizer with _step_supports_amp_scaling.  Per element, every a + s * b one fused multiply-add:
+ *   g0 = grad_scale ? g * (float)(1.0 / (double)*grad_scale) : g
+ *   g1 = wd != 0 ? fma(wd, p, g0) : g0
+ *   b1 = momentum != 0 ? fma(momentum, b, g1) : g1          (b starts at zero: the first step gives b1 = g1, torch's clone)
+ *   d  = nesterov ? fma(momentum, b1, g1) : b1
+ *   p  <- fma(-lr, d, p);   b <- b1 when momentum != 0 (buf may be NULL in a group whose momentum is 0)
+ * With found_inf given and *found_inf != 0 nothing is written.
+ *
+ * cft_ema_update: e <- fma(one_minus_d, m, d * e) over every segment (e = the EMA tensor, m = the model's); d and one_minus_d are
+ * each computed in double by the caller and rounded to float, as `v *= d; v += (1. - d) * msd[k]` does with Python scalars.
+ */
+#define CFT_OPTIM_CHUNK 4096
+#define CFT_OPTIM_MAX_BLOCKS 2048
+#define CFT_OPTIM_MAX_GROUPS 8
+#define CFT_SGD_SEG_BYTES 40
+#define CFT_EMA_SEG_BYTES 24
+#define CFT_OPTIM_WORK_BYTES 16
+typedef struct { float* p; const float* g; float* buf; long n; long group; } cft_sgd_seg_t;
+typedef struct { float* e; const float* m; long n; } cft_ema_seg_t;
+typedef struct { int seg; int pad; long start; } cft_optim_work_t;
+int cft_sgd_step(const void* table_dev, const void* table_host, int nseg, long nwork, int chunk, int max_blocks,
+                 const float* hyper_host, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
+int cft_ema_update(const void* table_dev, const void* table_host, int nseg, long nwork, int chunk, int max_blocks,
+                   float d, float one_minus_d, void* stream);
 
 #ifdef __cplusplus
 }

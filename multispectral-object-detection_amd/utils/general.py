@@ -3,6 +3,8 @@
 `utils/general.py:455-543`, as ONE batched HIP kernel instead of a Python loop over images around
 `torchvision.ops.nms`."""
 import glob
+import math
+import os
 import re
 from pathlib import Path
 
@@ -176,3 +178,46 @@ def save_one_box(xyxy, im, file='image.jpg', gain=1.02, pad=10, square=False, BG
         return None
     Image.fromarray(crop[..., ::-1].copy() if BGR else crop).save(str(path))
     return path
+
+
+def one_cycle(y1=0.0, y2=1.0, steps=100):
+    """The reference's learning-rate curve (utils/general.py:220-222): a half cosine from ``y1`` at ``x = 0`` to ``y2`` at ``x = steps``,
+    as a function for ``lr_scheduler.LambdaLR`` (``train.py:572``)."""
+    def curve(x):
+        return ((1 - math.cos(x * math.pi / steps)) / 2) * (y2 - y1) + y1
+    return curve
+
+
+def save_checkpoint(path, epoch, best_fitness, model, ema, optimizer, training_results=None):
+    """Write the checkpoint dictionary of ``train.py:850-858``: ``model`` and ``ema`` as half-precision copies of the (unwrapped)
+    model and of ``ema.ema``, ``updates``, the optimiser's state dict, ``wandb_id`` None.  The copies carry parameters, buffers and
+    attributes but no packed weights, plans or captured graphs, so a model in use can be saved.  ``compat.attempt_load`` reads it."""
+    from .torch_utils import de_parallel, detached_copy
+    ckpt = {'epoch': epoch,
+            'best_fitness': best_fitness,
+            'training_results': training_results,
+            'model': detached_copy(de_parallel(model)).half(),
+            'ema': detached_copy(ema.ema).half() if ema is not None else None,
+            'updates': ema.updates if ema is not None else None,
+            'optimizer': optimizer.state_dict() if optimizer is not None else None,
+            'wandb_id': None}
+    torch.save(ckpt, path)
+    return ckpt
+
+
+def strip_optimizer(f='best.pt', s=''):
+    """Finalise a checkpoint as the reference does (utils/general.py:546-559): the EMA replaces the model, the optimiser, the
+    training results, the W&B id, ``ema`` and ``updates`` become None, ``epoch`` -1, the model half precision and without grad.
+    Written over ``f``, or to ``s`` if given."""
+    x = torch.load(f, map_location=torch.device('cpu'), weights_only=False)
+    if x.get('ema'):
+        x['model'] = x['ema']
+    for k in 'optimizer', 'training_results', 'wandb_id', 'ema', 'updates':
+        x[k] = None
+    x['epoch'] = -1
+    x['model'].half()
+    for p in x['model'].parameters():
+        p.requires_grad = False
+    torch.save(x, s or f)
+    mb = os.path.getsize(s or f) / 1E6
+    print(f"Optimizer stripped from {f},{(' saved as %s,' % s) if s else ''} {mb:.1f}MB")
