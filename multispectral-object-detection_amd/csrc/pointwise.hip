@@ -1,6 +1,9 @@
 // Bandwidth-bound kernels of the two-stream YOLOv5 + CFT forward (gfx950): Focus space-to-depth,
 // SPP max pools, nearest-upsample/concat copy, Add/Add2, CFT tokeniser (adaptive avg-pool +
 // pos_emb), LayerNorm, CFT de-tokeniser (bilinear upsample + residual add) and Detect decode.
+// The three CFT token operations have ONE kernel source each; their variants are template parameters:
+// gpt_tokenize_kernel<T, VA, HA> and gpt_upsample_kernel<T, DUAL, VA, HA> (the 8 x 8 anchor grid at compile
+// time, or VA = 0: any grid from the arguments) and layernorm_kernel<MAXV, REDUCE> (with the split-K fold).
 // All tensors are NHWC and are moved in 16-byte granules (8 bf16 / 4 f32) per lane so that a
 // wave's accesses coalesce into full 128-B lines.
 #include "cft_common.h"
@@ -356,18 +359,49 @@ extern "C" int cft_add(const void* a, int lda, int aoff, const void* b, int ldb,
   return cft_check_launch("add_kernel");
 }
 
+// ------------------------------------------------------------------------------- CFT token kernels: shared host helpers
+// The entry points of one family share a validate-and-launch helper; `who` is the entry point that was called, so every
+// message still begins with its name.
+static int cft_fail(const char* who, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  cft_set_error(buf);
+  return CFT_EINVAL;
+}
+#define CFT_REQUIRE_WHO(cond, what) \
+  do {                              \
+    if (!(cond)) return cft_fail(who, what); \
+  } while (0)
+
+#define CFT_GRID_RULE "anchor grid must satisfy 1 <= va, ha and va * ha <= 1024"
+static inline bool cft_grid_ok(int va, int ha) { return va >= 1 && ha >= 1 && va * ha <= 1024; }
+
+// A channel slice of an NHWC tensor as the entry points receive it: pointer, row pitch and channel offset in elements.
+struct ChanRef {
+  const void* p;
+  int ld, off;
+  bool aligned(int ge) const { return p == nullptr || (ld % ge == 0 && off % ge == 0); }
+  unsigned char* ptr() const { return (unsigned char*)p; }
+};
+
 // ------------------------------------------------------------------------------- CFT tokeniser
-// grid = B*128 token cells; each thread owns channel granules and walks the pooling window.
-template <typename T>
+// tokens = AdaptiveAvgPool2d((va, ha)) of both streams (T = 2 * va * ha tokens, RGB cells 0 .. va*ha-1 then IR) + pos_emb.
+// grid = B * T token cells; each thread owns channel granules and walks the pooling window.  VA, HA > 0 fix the grid at compile
+// time (the 8 x 8 default: shifts instead of divisions); VA == 0 reads it from the arguments.  Every instantiation forms an
+// output element by the same expression: bit-identical at equal grids.
+template <typename T, int VA, int HA>
 __global__ void __launch_bounds__(256) gpt_tokenize_kernel(const unsigned char* rgb, long ld_rgb_b, long off_rgb_b,
                                                            const unsigned char* ir, long ld_ir_b, long off_ir_b,
                                                            const float* __restrict__ pos_emb, float* __restrict__ tokens,
-                                                           int H, int W, int C) {
+                                                           int H, int W, int C, int va_arg, int ha_arg) {
   constexpr int GE = Elem<T>::GE;
-  const int cell = blockIdx.x & 127, b = blockIdx.x >> 7;
-  const int s = cell >> 6, i = (cell >> 3) & 7, j = cell & 7;
-  const int h0 = (i * H) / 8, h1 = ((i + 1) * H + 7) / 8;
-  const int w0 = (j * W) / 8, w1 = ((j + 1) * W + 7) / 8;
+  const int va = VA ? VA : va_arg, ha = HA ? HA : ha_arg;
+  const int ncell = va * ha, ntok = 2 * ncell;
+  const int b = blockIdx.x / ntok, cell = blockIdx.x - b * ntok;
+  const int s = cell >= ncell ? 1 : 0, r = cell - s * ncell;
+  const int i = r / ha, j = r - i * ha;
+  const int h0 = (i * H) / va, h1 = ((i + 1) * H + va - 1) / va;     // AdaptiveAvgPool2d windows (overlap when H < va)
+  const int w0 = (j * W) / ha, w1 = ((j + 1) * W + ha - 1) / ha;
   const unsigned char* src = s ? ir : rgb;
   const long ldb = s ? ld_ir_b : ld_rgb_b, offb = s ? off_ir_b : off_rgb_b;
   const float inv = 1.0f / (float)((h1 - h0) * (w1 - w0));
@@ -382,92 +416,59 @@ __global__ void __launch_bounds__(256) gpt_tokenize_kernel(const unsigned char* 
 #pragma unroll
         for (int e = 0; e < GE; ++e) acc[e] += f[e];
       }
-    float* o = tokens + ((long)b * 128 + cell) * C + cg * GE;
+    float* o = tokens + ((long)b * ntok + cell) * C + cg * GE;
     const float* pe = pos_emb + (long)cell * C + cg * GE;
 #pragma unroll
     for (int e = 0; e < GE; ++e) o[e] = acc[e] * inv + pe[e];
   }
 }
 
-extern "C" int cft_gpt_tokenize(const void* rgb, int ld_rgb, int off_rgb, const void* ir, int ld_ir, int off_ir,
-                                const float* pos_emb, float* tokens, int B, int H, int W, int C,
-                                int dtype, void* stream) {
-  CFT_REQUIRE(rgb && ir && pos_emb && tokens, "cft_gpt_tokenize: null pointer");
-  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_tokenize: bad dtype");
-  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
-  CFT_REQUIRE(C % ge == 0 && ld_rgb % ge == 0 && off_rgb % ge == 0 && ld_ir % ge == 0 && off_ir % ge == 0, "cft_gpt_tokenize: not granule aligned");
-  CFT_REQUIRE(B > 0 && H >= 1 && W >= 1, "cft_gpt_tokenize: bad shape");
+template <int VA, int HA>
+static int gpt_tokenize_launch(const char* who, ChanRef rgb, ChanRef ir, const float* pos_emb, float* tokens,
+                               int B, int H, int W, int C, int va, int ha, int dtype, void* stream) {
+  CFT_REQUIRE_WHO(rgb.p && ir.p && pos_emb && tokens, "null pointer");
+  CFT_REQUIRE_WHO(cft_is_dtype(dtype), "bad dtype");
+  const int ge = cft_granule(dtype);
+  const long es = cft_elem_size(dtype);
+  CFT_REQUIRE_WHO(C % ge == 0 && rgb.aligned(ge) && ir.aligned(ge), "not granule aligned");
+  CFT_REQUIRE_WHO(B > 0 && H >= 1 && W >= 1, "bad shape");
+  if constexpr (VA == 0) {
+    CFT_REQUIRE_WHO(cft_grid_ok(va, ha), CFT_GRID_RULE);
+    CFT_REQUIRE_WHO((long)B * 2 * va * ha < (1L << 31), "too many tokens");
+  }
   int threads = C / ge;
   threads = threads < 64 ? 64 : (threads > 256 ? 256 : ((threads + 63) / 64) * 64);
-  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gpt_tokenize_kernel<T>, dim3(B * 128), dim3(threads), 0, as_stream(stream), (const unsigned char*)rgb, (long)ld_rgb * es, (long)off_rgb * es,
-                                                   (const unsigned char*)ir, (long)ld_ir * es, (long)off_ir * es, pos_emb, tokens, H, W, C));
+  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gpt_tokenize_kernel<T, VA, HA>), dim3(B * 2 * va * ha), dim3(threads), 0, as_stream(stream),
+                                                   rgb.ptr(), rgb.ld * es, rgb.off * es, ir.ptr(), ir.ld * es, ir.off * es, pos_emb, tokens, H, W, C, va, ha));
   return cft_check_launch("gpt_tokenize_kernel");
 }
 
+extern "C" int cft_gpt_tokenize(const void* rgb, int ld_rgb, int off_rgb, const void* ir, int ld_ir, int off_ir,
+                                const float* pos_emb, float* tokens, int B, int H, int W, int C,
+                                int dtype, void* stream) {
+  return gpt_tokenize_launch<8, 8>("cft_gpt_tokenize", {rgb, ld_rgb, off_rgb}, {ir, ld_ir, off_ir}, pos_emb, tokens, B, H, W, C, 8, 8, dtype, stream);
+}
+
+// Always the run-time-grid instantiation, also at (8, 8).
+extern "C" int cft_gpt_tokenize_grid(const void* rgb, int ld_rgb, int off_rgb, const void* ir, int ld_ir, int off_ir,
+                                     const float* pos_emb, float* tokens, int B, int H, int W, int C, int va, int ha,
+                                     int dtype, void* stream) {
+  return gpt_tokenize_launch<0, 0>("cft_gpt_tokenize_grid", {rgb, ld_rgb, off_rgb}, {ir, ld_ir, off_ir}, pos_emb, tokens, B, H, W, C, va, ha, dtype, stream);
+}
+
 // ------------------------------------------------------------------------------- LayerNorm
-// One wave64 per row (C <= 64*32 floats kept in registers as float4 chunks), 4 rows per workgroup.
-template <int MAXV>
-__global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, unsigned char* __restrict__ y,
-                                                        long rows, int C, float eps, int out_dtype) {
+// One wave64 per row (C <= 64*MAXV float4 kept in registers), 4 rows per workgroup.  REDUCE first folds split-K partial sums into
+// the residual stream: x[row] += parts[0][row] + parts[1][row] + ... (fixed order; x is written back), then y = LayerNorm(x); the
+// row lives in registers between the two steps.  The REDUCE-only arguments come last: the plain form then finds its own within the
+// first 64 bytes of the kernarg segment (measurably faster than behind them, profiles/pointwise_dedupe.md).
+template <int MAXV, bool REDUCE>
+__global__ void __launch_bounds__(256) layernorm_kernel(float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        unsigned char* __restrict__ y, long rows, int C, float eps, int out_dtype,
+                                                        const float* __restrict__ parts, int nparts, long part_stride) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int nv = C >> 2;  // float4 per row
-  const float4* xr = reinterpret_cast<const float4*>(x + row * C);
-  float4 v[MAXV];
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int idx = lane + k * 64;
-    v[k] = idx < nv ? xr[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
-    s += v[k].x + v[k].y + v[k].z + v[k].w;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const float mean = s / (float)C;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int idx = lane + k * 64;
-    if (idx < nv) {
-      const float a = v[k].x - mean, b = v[k].y - mean, c = v[k].z - mean, d = v[k].w - mean;
-      q += a * a + b * b + c * c + d * d;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-  const float rstd = rsqrtf(q / (float)C + eps);
-#pragma unroll
-  for (int k = 0; k < MAXV; ++k) {
-    const int idx = lane + k * 64;
-    if (idx < nv) {
-      const float4 gm = reinterpret_cast<const float4*>(gamma)[idx];
-      const float4 bt = reinterpret_cast<const float4*>(beta)[idx];
-      float o[4] = {(v[k].x - mean) * rstd * gm.x + bt.x, (v[k].y - mean) * rstd * gm.y + bt.y,
-                    (v[k].z - mean) * rstd * gm.z + bt.z, (v[k].w - mean) * rstd * gm.w + bt.w};
-      if (out_dtype == CFT_F32) {
-        *reinterpret_cast<float4*>(y + (row * C + idx * 4L) * 4) = *reinterpret_cast<float4*>(o);
-      } else {
-        uint2 pk;
-        if (out_dtype == CFT_BF16) { pk.x = pack_bf16x2(o[0], o[1]); pk.y = pack_bf16x2(o[2], o[3]); }
-        else { pk.x = pack_f16x2(o[0], o[1]); pk.y = pack_f16x2(o[2], o[3]); }
-        *reinterpret_cast<uint2*>(y + (row * C + idx * 4L) * 2) = pk;
-      }
-    }
-  }
-}
-
-// LayerNorm that first folds split-K partial sums into the residual stream: x[row] += parts[0][row] + parts[1][row] + ... (fixed order;
-// x is written back), then y = LayerNorm(x).  One wave per row, the row lives in registers between the two steps.
-template <int MAXV>
-__global__ void __launch_bounds__(256) layernorm_reduce_kernel(float* __restrict__ x, const float* __restrict__ parts, int nparts, long part_stride,
-                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                               unsigned char* __restrict__ y, long rows, int C, float eps, int out_dtype) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int nv = C >> 2;
   float4* xr = reinterpret_cast<float4*>(x + row * C);
   float4 v[MAXV];
   float s = 0.f;
@@ -477,11 +478,13 @@ __global__ void __launch_bounds__(256) layernorm_reduce_kernel(float* __restrict
     v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (idx < nv) {
       float4 a = xr[idx];
-      for (int sp = 0; sp < nparts; ++sp) {
-        const float4 q = reinterpret_cast<const float4*>(parts + sp * part_stride + row * C)[idx];
-        a.x += q.x; a.y += q.y; a.z += q.z; a.w += q.w;
+      if constexpr (REDUCE) {
+        for (int sp = 0; sp < nparts; ++sp) {
+          const float4 q = reinterpret_cast<const float4*>(parts + sp * part_stride + row * C)[idx];
+          a.x += q.x; a.y += q.y; a.z += q.z; a.w += q.w;
+        }
+        xr[idx] = a;
       }
-      xr[idx] = a;
       v[k] = a;
     }
     s += v[k].x + v[k].y + v[k].z + v[k].w;
@@ -521,260 +524,66 @@ __global__ void __launch_bounds__(256) layernorm_reduce_kernel(float* __restrict
   }
 }
 
-// x (fp32 [rows][C], updated in place) += parts[0 .. nparts) (fp32 [nparts][rows][C], e.g. from cft_linear_splitk); y = LayerNorm(x).
-extern "C" int cft_layernorm_reduce(float* x, const float* parts, int nparts, const float* gamma, const float* beta, void* y,
-                                    long rows, int C, float eps, int out_dtype, void* stream) {
-  CFT_REQUIRE(x && parts && gamma && beta && y, "cft_layernorm_reduce: null pointer");
-  CFT_REQUIRE(nparts >= 1 && nparts <= 8, "cft_layernorm_reduce: 1 <= nparts <= 8");
-  CFT_REQUIRE(C % 4 == 0 && C >= 4 && C <= 4096, "cft_layernorm_reduce: C must be a multiple of 4 and <= 4096");
-  CFT_REQUIRE(cft_is_dtype(out_dtype), "cft_layernorm_reduce: bad out dtype");
-  CFT_REQUIRE(rows > 0, "cft_layernorm_reduce: rows must be positive");
+// The guards that both entry points share, then the launch with the smallest MAXV that holds the row.
+template <bool REDUCE>
+static int layernorm_launch(const char* who, float* x, const float* parts, int nparts, const float* gamma, const float* beta, void* y,
+                            long rows, int C, float eps, int out_dtype, void* stream) {
+  CFT_REQUIRE_WHO(C % 4 == 0 && C >= 4 && C <= 4096, "C must be a multiple of 4 and <= 4096");
+  CFT_REQUIRE_WHO(cft_is_dtype(out_dtype), "bad out dtype");
+  CFT_REQUIRE_WHO(rows > 0, "rows must be positive");
   const int nv = C >> 2;
-  const long grid = (rows + 3) / 4;
-  const long ps = rows * (long)C;
-  if (nv <= 64 * 2)
-    hipLaunchKernelGGL(layernorm_reduce_kernel<2>, dim3(grid), dim3(256), 0, as_stream(stream), x, parts, nparts, ps, gamma, beta, (unsigned char*)y, rows, C, eps, out_dtype);
-  else if (nv <= 64 * 5)
-    hipLaunchKernelGGL(layernorm_reduce_kernel<5>, dim3(grid), dim3(256), 0, as_stream(stream), x, parts, nparts, ps, gamma, beta, (unsigned char*)y, rows, C, eps, out_dtype);
-  else
-    hipLaunchKernelGGL(layernorm_reduce_kernel<16>, dim3(grid), dim3(256), 0, as_stream(stream), x, parts, nparts, ps, gamma, beta, (unsigned char*)y, rows, C, eps, out_dtype);
-  return cft_check_launch("layernorm_reduce_kernel");
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((rows + 3) / 4), dim3(256), 0, as_stream(stream), x, gamma, beta, (unsigned char*)y, rows, C, eps, out_dtype,
+                       parts, nparts, rows * (long)C);
+  };
+  if (nv <= 64 * 2) launch(layernorm_kernel<2, REDUCE>);
+  else if (nv <= 64 * 5) launch(layernorm_kernel<5, REDUCE>);
+  else launch(layernorm_kernel<16, REDUCE>);
+  return cft_check_launch(REDUCE ? "layernorm_kernel (reduce)" : "layernorm_kernel");
 }
 
 extern "C" int cft_layernorm(const float* x, const float* gamma, const float* beta, void* y,
                              long rows, int C, float eps, int out_dtype, void* stream) {
   CFT_REQUIRE(x && gamma && beta && y, "cft_layernorm: null pointer");
-  CFT_REQUIRE(C % 4 == 0 && C >= 4 && C <= 4096, "cft_layernorm: C must be a multiple of 4 and <= 4096");
-  CFT_REQUIRE(cft_is_dtype(out_dtype), "cft_layernorm: bad out dtype");
-  CFT_REQUIRE(rows > 0, "cft_layernorm: rows must be positive");
-  const int grid = (int)((rows + 3) / 4);
-  const int nv = C / 4;
-  const int of32 = out_dtype;
-  if (nv <= 64 * 2)
-    hipLaunchKernelGGL(layernorm_kernel<2>, dim3(grid), dim3(256), 0, as_stream(stream), x, gamma, beta, (unsigned char*)y, rows, C, eps, of32);
-  else if (nv <= 64 * 5)
-    hipLaunchKernelGGL(layernorm_kernel<5>, dim3(grid), dim3(256), 0, as_stream(stream), x, gamma, beta, (unsigned char*)y, rows, C, eps, of32);
-  else
-    hipLaunchKernelGGL(layernorm_kernel<16>, dim3(grid), dim3(256), 0, as_stream(stream), x, gamma, beta, (unsigned char*)y, rows, C, eps, of32);
-  return cft_check_launch("layernorm_kernel");
+  return layernorm_launch<false>("cft_layernorm", const_cast<float*>(x), nullptr, 0, gamma, beta, y, rows, C, eps, out_dtype, stream);   // (x is only read)
+}
+
+// x (fp32 [rows][C], updated in place) += parts[0 .. nparts) (fp32 [nparts][rows][C], e.g. from cft_linear_splitk); y = LayerNorm(x).
+extern "C" int cft_layernorm_reduce(float* x, const float* parts, int nparts, const float* gamma, const float* beta, void* y,
+                                    long rows, int C, float eps, int out_dtype, void* stream) {
+  CFT_REQUIRE(x && parts && gamma && beta && y, "cft_layernorm_reduce: null pointer");
+  CFT_REQUIRE(nparts >= 1 && nparts <= 8, "cft_layernorm_reduce: 1 <= nparts <= 8");
+  return layernorm_launch<true>("cft_layernorm_reduce", x, parts, nparts, gamma, beta, y, rows, C, eps, out_dtype, stream);
 }
 
 // ------------------------------------------------------------------------------- CFT de-tokeniser
-// out = base + bilinear(tokens 8x8 -> HxW), PyTorch align_corners=False source index:
-// src = (dst + 0.5) * (8 / size) - 0.5, clamped at 0; neighbour clamped at 7.
-// One workgroup per output image row (b, y): the two token rows that the bilinear filter touches are blended
-// in y ONCE into LDS (8 cells x C floats), then every output granule needs two LDS reads instead of four
-// 32-byte token fetches from L2 (the token traffic was 8x the output traffic).
-template <typename T>
-__global__ void __launch_bounds__(256) gpt_upsample_add_kernel(const float* __restrict__ tokens, int s,
-                                                               const unsigned char* base, long ldb_b, long boff_b,
-                                                               unsigned char* out, long ldo_b, long ooff_b,
-                                                               int B, int H, int W, int C) {
-  constexpr int GE = Elem<T>::GE;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* R = reinterpret_cast<float*>(smem);          // [8][C]
-  const int b = blockIdx.x / H, y = blockIdx.x - b * H;
-  float fy = ((float)y + 0.5f) * (8.0f / (float)H) - 0.5f; fy = fy < 0.f ? 0.f : fy;
-  const int y0 = (int)fy, y1 = y0 + (y0 < 7 ? 1 : 0);
-  const float ly = fy - (float)y0, hy = 1.f - ly;
-  const float* t0 = tokens + ((long)b * 128 + s * 64 + y0 * 8) * C;
-  const float* t1 = tokens + ((long)b * 128 + s * 64 + y1 * 8) * C;
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {          // 8*C/4 float4
-    const float4 a = reinterpret_cast<const float4*>(t0)[i], c = reinterpret_cast<const float4*>(t1)[i];
-    reinterpret_cast<float4*>(R)[i] = make_float4(hy * a.x + ly * c.x, hy * a.y + ly * c.y, hy * a.z + ly * c.z, hy * a.w + ly * c.w);
-  }
-  __syncthreads();
-  const int gpp = C / GE;
-  const float sx = 8.0f / (float)W;
-  const long rowpix = ((long)b * H + y) * W;
-  for (int idx = threadIdx.x; idx < W * gpp; idx += blockDim.x) {
-    const int x = idx / gpp, cg = idx - x * gpp;
-    float fx = ((float)x + 0.5f) * sx - 0.5f; fx = fx < 0.f ? 0.f : fx;
-    const int x0 = (int)fx, x1 = x0 + (x0 < 7 ? 1 : 0);
-    const float lx = fx - (float)x0, hx = 1.f - lx;
-    const float* r0 = R + x0 * C + cg * GE;
-    const float* r1 = R + x1 * C + cg * GE;
-    float v[GE];
-    const long pix = rowpix + x;
-    if (base != nullptr) {
-      Elem<T>::unpack(*reinterpret_cast<const gran_t*>(base + pix * ldb_b + boff_b + cg * 16L), v);
-    } else {
-#pragma unroll
-      for (int e = 0; e < GE; ++e) v[e] = 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < GE; ++e) v[e] += hx * r0[e] + lx * r1[e];
-    *reinterpret_cast<gran_t*>(out + pix * ldo_b + ooff_b + cg * 16L) = Elem<T>::pack(v);
-  }
-}
-
-extern "C" int cft_gpt_upsample_add(const float* tokens, int s, const void* base, int ldb, int boff,
-                                    void* out, int ldo, int ooff, int B, int H, int W, int C,
-                                    int dtype, void* stream) {
-  CFT_REQUIRE(tokens && out, "cft_gpt_upsample_add: null pointer");
-  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add: bad dtype");
-  CFT_REQUIRE(s == 0 || s == 1, "cft_gpt_upsample_add: stream index must be 0 or 1");
-  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
-  CFT_REQUIRE(C % ge == 0 && ldo % ge == 0 && ooff % ge == 0 && (base == nullptr || (ldb % ge == 0 && boff % ge == 0)), "cft_gpt_upsample_add: not granule aligned");
-  CFT_REQUIRE(C % 4 == 0 && (long)B * H < (1L << 31), "cft_gpt_upsample_add: C must be a multiple of 4");
-  const int grid = B * H;
-  const size_t smem = (size_t)8 * C * sizeof(float);
-  CFT_REQUIRE(smem <= 64 * 1024, "cft_gpt_upsample_add: C too large for the LDS row (C <= 2048)");
-  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gpt_upsample_add_kernel<T>, dim3(grid), dim3(256), smem, as_stream(stream), tokens, s, (const unsigned char*)base, (long)ldb * es, (long)boff * es,
-                                                   (unsigned char*)out, (long)ldo * es, (long)ooff * es, B, H, W, C));
-  return cft_check_launch("gpt_upsample_add_kernel");
-}
-
-// Both streams of a CFT block in ONE launch, with the Add that follows them in the graph (yaml rows 11-12 + 29 of the x3 configs):
-//   out0 = base0 + up(tokens[:, :64]),  out1 = base1 + up(tokens[:, 64:]),  sum = out0 + out1 (optional)
+// out = base + bilinear(tokens va x ha -> H x W), PyTorch align_corners=False source index:
+// src = (dst + 0.5) * (va / size) - 0.5, clamped at 0; neighbour clamped at va - 1.
+// One workgroup per output image row (b, y): the two token rows that the bilinear filter touches are blended in y ONCE into LDS
+// ([ha][CW] floats per stream), then every output granule needs two LDS reads instead of four 32-byte token fetches from L2 (the
+// token traffic was 8x the output traffic).  The row is staged one channel chunk of CW channels at a time, so any ha * C fits;
+// CW = C (one trip) when the whole row fits the budget.
+// DUAL = false: stream s of tokens, optional base0.  DUAL = true: both streams of a CFT block in ONE launch, with the Add that follows
+// them in the graph (yaml rows 11-12 + 29 of the x3 configs):
+//   out0 = base0 + up(tokens[:, :T/2]),  out1 = base1 + up(tokens[:, T/2:]),  sum = out0 + out1 (optional)
 // (models/common.py:626-637 twice + Add2 :238-243 twice + Add :228-229).  One launch instead of three, the two base maps are read once
 // instead of once + once more by Add, and the sum is formed from the UNROUNDED fp32 sums: one rounding per output tensor (the
 // reference adds in fp32 throughout; profiles/r04_bf16_sites.md lists Add / Add2 among the activation-side rounding sites).
-template <typename T>
-__global__ void __launch_bounds__(256) gpt_upsample_add2_kernel(const float* __restrict__ tokens,
-                                                                const unsigned char* base0, long ldb0_b, long boff0_b,
-                                                                const unsigned char* base1, long ldb1_b, long boff1_b,
-                                                                unsigned char* out0, long ldo0_b, long ooff0_b,
-                                                                unsigned char* out1, long ldo1_b, long ooff1_b,
-                                                                unsigned char* sum, long lds_b, long soff_b,
-                                                                int B, int H, int W, int C) {
-  constexpr int GE = Elem<T>::GE;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* R = reinterpret_cast<float*>(smem);          // [2][8][C]: the row's vertical interpolation of both streams' tokens
-  const int b = blockIdx.x / H, y = blockIdx.x - b * H;
-  float fy = ((float)y + 0.5f) * (8.0f / (float)H) - 0.5f; fy = fy < 0.f ? 0.f : fy;
-  const int y0 = (int)fy, y1 = y0 + (y0 < 7 ? 1 : 0);
-  const float ly = fy - (float)y0, hy = 1.f - ly;
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const float* t0 = tokens + ((long)b * 128 + s * 64 + y0 * 8) * C;
-    const float* t1 = tokens + ((long)b * 128 + s * 64 + y1 * 8) * C;
-    for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-      const float4 a = reinterpret_cast<const float4*>(t0)[i], c = reinterpret_cast<const float4*>(t1)[i];
-      reinterpret_cast<float4*>(R + s * 8 * C)[i] = make_float4(hy * a.x + ly * c.x, hy * a.y + ly * c.y, hy * a.z + ly * c.z, hy * a.w + ly * c.w);
-    }
-  }
-  __syncthreads();
-  const int gpp = C / GE;
-  const float sx = 8.0f / (float)W;
-  const long rowpix = ((long)b * H + y) * W;
-  for (int idx = threadIdx.x; idx < W * gpp; idx += blockDim.x) {
-    const int x = idx / gpp, cg = idx - x * gpp;
-    float fx = ((float)x + 0.5f) * sx - 0.5f; fx = fx < 0.f ? 0.f : fx;
-    const int x0 = (int)fx, x1 = x0 + (x0 < 7 ? 1 : 0);
-    const float lx = fx - (float)x0, hx = 1.f - lx;
-    const long pix = rowpix + x;
-    float v0[GE], v1[GE];
-    Elem<T>::unpack(*reinterpret_cast<const gran_t*>(base0 + pix * ldb0_b + boff0_b + cg * 16L), v0);
-    Elem<T>::unpack(*reinterpret_cast<const gran_t*>(base1 + pix * ldb1_b + boff1_b + cg * 16L), v1);
-    const float* r0 = R + x0 * C + cg * GE;
-    const float* r1 = R + x1 * C + cg * GE;
-#pragma unroll
-    for (int e = 0; e < GE; ++e) {            // the same expression as gpt_upsample_add_kernel: out0 / out1 are bit-identical to it
-      v0[e] += hx * r0[e] + lx * r1[e];
-      v1[e] += hx * r0[8 * C + e] + lx * r1[8 * C + e];
-    }
-    *reinterpret_cast<gran_t*>(out0 + pix * ldo0_b + ooff0_b + cg * 16L) = Elem<T>::pack(v0);
-    *reinterpret_cast<gran_t*>(out1 + pix * ldo1_b + ooff1_b + cg * 16L) = Elem<T>::pack(v1);
-    if (sum != nullptr) {
-#pragma unroll
-      for (int e = 0; e < GE; ++e) v0[e] += v1[e];
-      *reinterpret_cast<gran_t*>(sum + pix * lds_b + soff_b + cg * 16L) = Elem<T>::pack(v0);
-    }
-  }
-}
-
-extern "C" int cft_gpt_upsample_add2(const float* tokens, const void* base0, int ldb0, int boff0, const void* base1, int ldb1, int boff1,
-                                     void* out0, int ldo0, int ooff0, void* out1, int ldo1, int ooff1, void* sum, int lds, int soff,
-                                     int B, int H, int W, int C, int dtype, void* stream) {
-  CFT_REQUIRE(tokens && base0 && base1 && out0 && out1, "cft_gpt_upsample_add2: null pointer");
-  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add2: bad dtype");
-  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
-  CFT_REQUIRE(C % ge == 0 && ldb0 % ge == 0 && boff0 % ge == 0 && ldb1 % ge == 0 && boff1 % ge == 0 && ldo0 % ge == 0 && ooff0 % ge == 0 &&
-              ldo1 % ge == 0 && ooff1 % ge == 0 && (sum == nullptr || (lds % ge == 0 && soff % ge == 0)), "cft_gpt_upsample_add2: not granule aligned");
-  CFT_REQUIRE(C % 4 == 0 && (long)B * H < (1L << 31), "cft_gpt_upsample_add2: C must be a multiple of 4");
-  const int smem = 2 * 8 * C * (int)sizeof(float);
-  CFT_REQUIRE(smem <= 128 * 1024, "cft_gpt_upsample_add2: C too large for the LDS rows (C <= 2048)");
-  CFT_DISPATCH_DTYPE(dtype, T, {
-    cft_allow_lds<&gpt_upsample_add2_kernel<T>>(128 * 1024);
-    hipLaunchKernelGGL(gpt_upsample_add2_kernel<T>, dim3(B * H), dim3(256), smem, as_stream(stream), tokens,
-                       (const unsigned char*)base0, (long)ldb0 * es, (long)boff0 * es, (const unsigned char*)base1, (long)ldb1 * es, (long)boff1 * es,
-                       (unsigned char*)out0, (long)ldo0 * es, (long)ooff0 * es, (unsigned char*)out1, (long)ldo1 * es, (long)ooff1 * es,
-                       (unsigned char*)sum, (long)lds * es, (long)soff * es, B, H, W, C);
-  });
-  return cft_check_launch("gpt_upsample_add2_kernel");
-}
-
-// ------------------------------------------------------------------------------- CFT tokeniser / de-tokeniser on a va x ha grid
-// The same as gpt_tokenize_kernel / gpt_upsample_add{,2}_kernel for a vert_anchors x horz_anchors grid (T = 2 * va * ha tokens, RGB
-// cells 0 .. va*ha-1 then IR).  At (8, 8) every output element is formed by the same expression as the 8x8 kernels: bit-identical.
-template <typename T>
-__global__ void __launch_bounds__(256) gpt_tokenize_grid_kernel(const unsigned char* rgb, long ld_rgb_b, long off_rgb_b,
-                                                                const unsigned char* ir, long ld_ir_b, long off_ir_b,
-                                                                const float* __restrict__ pos_emb, float* __restrict__ tokens,
-                                                                int H, int W, int C, int va, int ha) {
-  constexpr int GE = Elem<T>::GE;
-  const int ncell = va * ha, ntok = 2 * ncell;
-  const int b = blockIdx.x / ntok, cell = blockIdx.x - b * ntok;
-  const int s = cell >= ncell ? 1 : 0, r = cell - s * ncell;
-  const int i = r / ha, j = r - i * ha;
-  const int h0 = (i * H) / va, h1 = ((i + 1) * H + va - 1) / va;     // AdaptiveAvgPool2d windows (overlap when H < va)
-  const int w0 = (j * W) / ha, w1 = ((j + 1) * W + ha - 1) / ha;
-  const unsigned char* src = s ? ir : rgb;
-  const long ldb = s ? ld_ir_b : ld_rgb_b, offb = s ? off_ir_b : off_rgb_b;
-  const float inv = 1.0f / (float)((h1 - h0) * (w1 - w0));
-  for (int cg = threadIdx.x; cg < C / GE; cg += blockDim.x) {
-    float acc[GE];
-#pragma unroll
-    for (int e = 0; e < GE; ++e) acc[e] = 0.f;
-    for (int y = h0; y < h1; ++y)
-      for (int x = w0; x < w1; ++x) {
-        float f[GE];
-        Elem<T>::unpack(*reinterpret_cast<const gran_t*>(src + (((long)b * H + y) * W + x) * ldb + offb + cg * 16L), f);
-#pragma unroll
-        for (int e = 0; e < GE; ++e) acc[e] += f[e];
-      }
-    float* o = tokens + ((long)b * ntok + cell) * C + cg * GE;
-    const float* pe = pos_emb + (long)cell * C + cg * GE;
-#pragma unroll
-    for (int e = 0; e < GE; ++e) o[e] = acc[e] * inv + pe[e];
-  }
-}
-
-extern "C" int cft_gpt_tokenize_grid(const void* rgb, int ld_rgb, int off_rgb, const void* ir, int ld_ir, int off_ir,
-                                     const float* pos_emb, float* tokens, int B, int H, int W, int C, int va, int ha,
-                                     int dtype, void* stream) {
-  CFT_REQUIRE(rgb && ir && pos_emb && tokens, "cft_gpt_tokenize_grid: null pointer");
-  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_tokenize_grid: bad dtype");
-  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
-  CFT_REQUIRE(C % ge == 0 && ld_rgb % ge == 0 && off_rgb % ge == 0 && ld_ir % ge == 0 && off_ir % ge == 0, "cft_gpt_tokenize_grid: not granule aligned");
-  CFT_REQUIRE(B > 0 && H >= 1 && W >= 1, "cft_gpt_tokenize_grid: bad shape");
-  CFT_REQUIRE(va >= 1 && ha >= 1 && va * ha <= 1024, "cft_gpt_tokenize_grid: anchor grid must satisfy 1 <= va, ha and va * ha <= 1024");
-  CFT_REQUIRE((long)B * 2 * va * ha < (1L << 31), "cft_gpt_tokenize_grid: too many tokens");
-  int threads = C / ge;
-  threads = threads < 64 ? 64 : (threads > 256 ? 256 : ((threads + 63) / 64) * 64);
-  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gpt_tokenize_grid_kernel<T>, dim3(B * 2 * va * ha), dim3(threads), 0, as_stream(stream),
-                                                   (const unsigned char*)rgb, (long)ld_rgb * es, (long)off_rgb * es,
-                                                   (const unsigned char*)ir, (long)ld_ir * es, (long)off_ir * es, pos_emb, tokens, H, W, C, va, ha));
-  return cft_check_launch("gpt_tokenize_grid_kernel");
-}
-
-// De-tokeniser on a va x ha grid: one workgroup per output image row (b, y), like gpt_upsample_add_kernel.  The y-blended token row
-// ([ha][CW] floats per stream) is staged in LDS one channel chunk of CW channels at a time, so any ha * C fits (CW = C when the whole
-// row fits the budget).  DUAL = false: stream s of tokens, optional base (one-stream form).  DUAL = true: both streams, both bases,
-// optional sum = out0 + out1 from the unrounded fp32 values (the two-stream + Add2 (+ Add) form of gpt_upsample_add2_kernel).
-template <typename T, bool DUAL>
-__global__ void __launch_bounds__(256) gpt_upsample_grid_kernel(const float* __restrict__ tokens, int s,
-                                                                const unsigned char* base0, long ldb0_b, long boff0_b,
-                                                                const unsigned char* base1, long ldb1_b, long boff1_b,
-                                                                unsigned char* out0, long ldo0_b, long ooff0_b,
-                                                                unsigned char* out1, long ldo1_b, long ooff1_b,
-                                                                unsigned char* sum, long lds_b, long soff_b,
-                                                                int B, int H, int W, int C, int va, int ha, int CW) {
+// VA, HA as in gpt_tokenize_kernel.  Every instantiation forms an output element by the same expression, whatever the chunking:
+// out0 / out1 of the dual form are bit-identical to the one-stream form, and the 8 x 8 instantiations to the run-time grid at (8, 8).
+template <typename T, bool DUAL, int VA, int HA>
+__global__ void __launch_bounds__(256) gpt_upsample_kernel(const float* __restrict__ tokens, int s,
+                                                           const unsigned char* base0, long ldb0_b, long boff0_b,
+                                                           const unsigned char* base1, long ldb1_b, long boff1_b,
+                                                           unsigned char* out0, long ldo0_b, long ooff0_b,
+                                                           unsigned char* out1, long ldo1_b, long ooff1_b,
+                                                           unsigned char* sum, long lds_b, long soff_b,
+                                                           int B, int H, int W, int C, int va_arg, int ha_arg, int CW) {
   constexpr int GE = Elem<T>::GE;
   constexpr int NS = DUAL ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* R = reinterpret_cast<float*>(smem);          // [NS][ha][CW]
+  const int va = VA ? VA : va_arg, ha = HA ? HA : ha_arg;
   const int ncell = va * ha;
   const int b = blockIdx.x / H, y = blockIdx.x - b * H;
   float fy = ((float)y + 0.5f) * ((float)va / (float)H) - 0.5f; fy = fy < 0.f ? 0.f : fy;
@@ -792,7 +601,8 @@ __global__ void __launch_bounds__(256) gpt_upsample_grid_kernel(const float* __r
       const float* t0 = tokens + ((long)b * 2 * ncell + st * ncell + y0 * ha) * C + c0;
       const float* t1 = tokens + ((long)b * 2 * ncell + st * ncell + y1 * ha) * C + c0;
       for (int i = threadIdx.x; i < ha * q4; i += blockDim.x) {
-        const int x = i / q4, k = i - x * q4;
+        int x = 0, k = i;                               // CW == C: the staged row is contiguous in the tokens and in LDS
+        if (CW != C) { x = i / q4; k = i - x * q4; }
         const float4 a = reinterpret_cast<const float4*>(t0 + (long)x * C)[k], c = reinterpret_cast<const float4*>(t1 + (long)x * C)[k];
         reinterpret_cast<float4*>(R + (ss * ha + x) * CW)[k] = make_float4(hy * a.x + ly * c.x, hy * a.y + ly * c.y, hy * a.z + ly * c.z, hy * a.w + ly * c.w);
       }
@@ -809,7 +619,7 @@ __global__ void __launch_bounds__(256) gpt_upsample_grid_kernel(const float* __r
       const float* r0 = R + x0 * CW + cgl * GE;
       const float* r1 = R + x1 * CW + cgl * GE;
       float v0[GE];
-      if (base0 != nullptr) {
+      if (DUAL || base0 != nullptr) {                 // (the dual form requires both bases: no branch between its two loads)
         Elem<T>::unpack(*reinterpret_cast<const gran_t*>(base0 + pix * ldb0_b + boff0_b + cb), v0);
       } else {
 #pragma unroll
@@ -839,11 +649,58 @@ __global__ void __launch_bounds__(256) gpt_upsample_grid_kernel(const float* __r
   }
 }
 
-// LDS budget of the de-tokeniser's staged row: 64 KiB; channel chunk = the widest multiple of 8 channels that fits.
+// LDS budget of the run-time-grid de-tokeniser's staged row: 64 KiB; channel chunk = the widest multiple of 8 channels that fits.
 static inline int gpt_upsample_grid_chunk(int C, int ha, int ns) {
   int cw = (16 * 1024) / (ns * ha);
   cw -= cw % 8;
   return C < cw ? C : cw;
+}
+
+// Alignment and size guards and the launch of all four de-tokeniser entry points (the caller has checked its pointers, dtype, stream
+// index and grid).  The 8 x 8 instantiations stage the whole row (CW = C): 64 KiB for one stream, 128 KiB (opt-in) for two.
+template <bool DUAL, int VA, int HA>
+static int gpt_upsample_launch(const char* who, const float* tokens, int s, ChanRef base0, ChanRef base1, ChanRef out0, ChanRef out1, ChanRef sum,
+                               int B, int H, int W, int C, int va, int ha, int dtype, void* stream) {
+  constexpr int NS = DUAL ? 2 : 1;
+  const int ge = cft_granule(dtype);
+  const long es = cft_elem_size(dtype);
+  CFT_REQUIRE_WHO(C % ge == 0 && base0.aligned(ge) && base1.aligned(ge) && out0.aligned(ge) && out1.aligned(ge) && sum.aligned(ge), "not granule aligned");
+  int cw = C;
+  if constexpr (VA != 0) {
+    CFT_REQUIRE_WHO(C % 4 == 0 && (long)B * H < (1L << 31), "C must be a multiple of 4");
+    CFT_REQUIRE_WHO((size_t)NS * HA * C * sizeof(float) <= (size_t)NS * 64 * 1024,
+                    DUAL ? "C too large for the LDS rows (C <= 2048)" : "C too large for the LDS row (C <= 2048)");
+  } else {
+    CFT_REQUIRE_WHO(C % 4 == 0 && C <= 2048 && B > 0 && H >= 1 && W >= 1 && (long)B * H < (1L << 31), "C must be a multiple of 4, <= 2048");
+    cw = gpt_upsample_grid_chunk(C, ha, NS);
+  }
+  const size_t smem = (size_t)NS * ha * cw * sizeof(float);
+  CFT_DISPATCH_DTYPE(dtype, T, {
+    if constexpr (DUAL && VA != 0) cft_allow_lds<&gpt_upsample_kernel<T, DUAL, VA, HA>>(128 * 1024);
+    hipLaunchKernelGGL((gpt_upsample_kernel<T, DUAL, VA, HA>), dim3(B * H), dim3(256), smem, as_stream(stream), tokens, s,
+                       base0.ptr(), base0.ld * es, base0.off * es, base1.ptr(), base1.ld * es, base1.off * es,
+                       out0.ptr(), out0.ld * es, out0.off * es, out1.ptr(), out1.ld * es, out1.off * es,
+                       sum.ptr(), sum.ld * es, sum.off * es, B, H, W, C, va, ha, cw);
+  });
+  return cft_check_launch("gpt_upsample_kernel");
+}
+
+extern "C" int cft_gpt_upsample_add(const float* tokens, int s, const void* base, int ldb, int boff,
+                                    void* out, int ldo, int ooff, int B, int H, int W, int C,
+                                    int dtype, void* stream) {
+  CFT_REQUIRE(tokens && out, "cft_gpt_upsample_add: null pointer");
+  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add: bad dtype");
+  CFT_REQUIRE(s == 0 || s == 1, "cft_gpt_upsample_add: stream index must be 0 or 1");
+  return gpt_upsample_launch<false, 8, 8>("cft_gpt_upsample_add", tokens, s, {base, ldb, boff}, {}, {out, ldo, ooff}, {}, {}, B, H, W, C, 8, 8, dtype, stream);
+}
+
+extern "C" int cft_gpt_upsample_add2(const float* tokens, const void* base0, int ldb0, int boff0, const void* base1, int ldb1, int boff1,
+                                     void* out0, int ldo0, int ooff0, void* out1, int ldo1, int ooff1, void* sum, int lds, int soff,
+                                     int B, int H, int W, int C, int dtype, void* stream) {
+  CFT_REQUIRE(tokens && base0 && base1 && out0 && out1, "cft_gpt_upsample_add2: null pointer");
+  CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add2: bad dtype");
+  return gpt_upsample_launch<true, 8, 8>("cft_gpt_upsample_add2", tokens, 0, {base0, ldb0, boff0}, {base1, ldb1, boff1}, {out0, ldo0, ooff0},
+                                         {out1, ldo1, ooff1}, {sum, lds, soff}, B, H, W, C, 8, 8, dtype, stream);
 }
 
 extern "C" int cft_gpt_upsample_add_grid(const float* tokens, int s, const void* base, int ldb, int boff,
@@ -852,17 +709,8 @@ extern "C" int cft_gpt_upsample_add_grid(const float* tokens, int s, const void*
   CFT_REQUIRE(tokens && out, "cft_gpt_upsample_add_grid: null pointer");
   CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add_grid: bad dtype");
   CFT_REQUIRE(s == 0 || s == 1, "cft_gpt_upsample_add_grid: stream index must be 0 or 1");
-  CFT_REQUIRE(va >= 1 && ha >= 1 && va * ha <= 1024, "cft_gpt_upsample_add_grid: anchor grid must satisfy 1 <= va, ha and va * ha <= 1024");
-  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
-  CFT_REQUIRE(C % ge == 0 && ldo % ge == 0 && ooff % ge == 0 && (base == nullptr || (ldb % ge == 0 && boff % ge == 0)), "cft_gpt_upsample_add_grid: not granule aligned");
-  CFT_REQUIRE(C % 4 == 0 && C <= 2048 && B > 0 && H >= 1 && W >= 1 && (long)B * H < (1L << 31), "cft_gpt_upsample_add_grid: C must be a multiple of 4, <= 2048");
-  const int cw = gpt_upsample_grid_chunk(C, ha, 1);
-  const size_t smem = (size_t)ha * cw * sizeof(float);
-  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gpt_upsample_grid_kernel<T, false>), dim3(B * H), dim3(256), smem, as_stream(stream), tokens, s,
-                                                   (const unsigned char*)base, (long)ldb * es, (long)boff * es, nullptr, 0L, 0L,
-                                                   (unsigned char*)out, (long)ldo * es, (long)ooff * es, nullptr, 0L, 0L, nullptr, 0L, 0L,
-                                                   B, H, W, C, va, ha, cw));
-  return cft_check_launch("gpt_upsample_grid_kernel");
+  CFT_REQUIRE(cft_grid_ok(va, ha), "cft_gpt_upsample_add_grid: " CFT_GRID_RULE);
+  return gpt_upsample_launch<false, 0, 0>("cft_gpt_upsample_add_grid", tokens, s, {base, ldb, boff}, {}, {out, ldo, ooff}, {}, {}, B, H, W, C, va, ha, dtype, stream);
 }
 
 extern "C" int cft_gpt_upsample_add2_grid(const float* tokens, const void* base0, int ldb0, int boff0, const void* base1, int ldb1, int boff1,
@@ -870,18 +718,9 @@ extern "C" int cft_gpt_upsample_add2_grid(const float* tokens, const void* base0
                                           int B, int H, int W, int C, int va, int ha, int dtype, void* stream) {
   CFT_REQUIRE(tokens && base0 && base1 && out0 && out1, "cft_gpt_upsample_add2_grid: null pointer");
   CFT_REQUIRE(cft_is_dtype(dtype), "cft_gpt_upsample_add2_grid: bad dtype");
-  CFT_REQUIRE(va >= 1 && ha >= 1 && va * ha <= 1024, "cft_gpt_upsample_add2_grid: anchor grid must satisfy 1 <= va, ha and va * ha <= 1024");
-  const int ge = cft_granule(dtype), es = cft_elem_size(dtype);
-  CFT_REQUIRE(C % ge == 0 && ldb0 % ge == 0 && boff0 % ge == 0 && ldb1 % ge == 0 && boff1 % ge == 0 && ldo0 % ge == 0 && ooff0 % ge == 0 &&
-              ldo1 % ge == 0 && ooff1 % ge == 0 && (sum == nullptr || (lds % ge == 0 && soff % ge == 0)), "cft_gpt_upsample_add2_grid: not granule aligned");
-  CFT_REQUIRE(C % 4 == 0 && C <= 2048 && B > 0 && H >= 1 && W >= 1 && (long)B * H < (1L << 31), "cft_gpt_upsample_add2_grid: C must be a multiple of 4, <= 2048");
-  const int cw = gpt_upsample_grid_chunk(C, ha, 2);
-  const size_t smem = (size_t)2 * ha * cw * sizeof(float);
-  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gpt_upsample_grid_kernel<T, true>), dim3(B * H), dim3(256), smem, as_stream(stream), tokens, 0,
-                                                   (const unsigned char*)base0, (long)ldb0 * es, (long)boff0 * es, (const unsigned char*)base1, (long)ldb1 * es, (long)boff1 * es,
-                                                   (unsigned char*)out0, (long)ldo0 * es, (long)ooff0 * es, (unsigned char*)out1, (long)ldo1 * es, (long)ooff1 * es,
-                                                   (unsigned char*)sum, (long)lds * es, (long)soff * es, B, H, W, C, va, ha, cw));
-  return cft_check_launch("gpt_upsample_grid_kernel");
+  CFT_REQUIRE(cft_grid_ok(va, ha), "cft_gpt_upsample_add2_grid: " CFT_GRID_RULE);
+  return gpt_upsample_launch<true, 0, 0>("cft_gpt_upsample_add2_grid", tokens, 0, {base0, ldb0, boff0}, {base1, ldb1, boff1}, {out0, ldo0, ooff0},
+                                         {out1, ldo1, ooff1}, {sum, lds, soff}, B, H, W, C, va, ha, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------- Detect decode

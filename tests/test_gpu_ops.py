@@ -322,6 +322,7 @@ def test_linear_splitk_and_layernorm_reduce(dev, dtype, rows, n, K, splits):
     want_y = torch.nn.functional.layer_norm(want_x, (pk.n,), gamma, beta, 1e-5)
     torch.cuda.synchronize()
     assert torch.equal(xr, want_x)                                           # fixed order: bit-exact running sum
+    assert torch.equal(y, ops.layernorm(want_x, gamma, beta, dtype))         # one kernel body: the plain LayerNorm of the same row
     assert (y.float() - want_y).abs().max().item() <= (1e-4 if dtype == torch.float32 else 4e-2)
     fc2 = ops.pack_conv(torch.zeros(1024, 4096), None, torch.bfloat16, device=dev)
     assert ops.splitk_choice(8192, fc2, torch.bfloat16) == 1            # 64 pairs: the partial-sum traffic costs more than the split gains
