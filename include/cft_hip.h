@@ -480,10 +480,17 @@ int cft_detect_boxes(const float* dets, const int* counts, int B, int max_det, c
  *   colors [nc, 3] uint8 in the images' channel order; text_color = c0 | c1 << 8 | c2 << 16
  *   names [nc, name_ld] uint8 character codes, name_len [nc] int (clamped to [0, name_ld]); name_ld in [1, 32]
  *   atlas [96, gh, gw] uint8 for the codes 32..127; gh, gw in [1, 64]; thickness in [1, 64]
+ * Two further flags serve plot_images (below); without them the output is what it was:
+ *   CFT_RENDER_CONF1   (with flag conf) the suffix is ' ' and d.d from word 5 read as tenths 0..10 ('%.1f', utils/plots.py:185), four characters;
+ *   CFT_RENDER_SIGNED  slot coordinates may be negative: they are clamped to [-2^24, 2^24] instead of [0, 2^24].  A box that starts left of
+ *                      or above its image draws exactly the part inside: its off-image edge is not pulled to the border and its label starts
+ *                      where the box starts.
  */
 #define CFT_RENDER_DESC_BYTES 48
 #define CFT_RENDER_LABELS 1
 #define CFT_RENDER_CONF 2
+#define CFT_RENDER_CONF1 4
+#define CFT_RENDER_SIGNED 8
 #define CFT_RENDER_MAX_NAME 32
 typedef struct {
   unsigned char* img_rgb;         /* HWC uint8, pixels contiguous */
@@ -495,6 +502,68 @@ typedef struct {
 int cft_detect_render(const void* desc_dev, const void* desc_host, int B, const int* boxes, int max_det, const unsigned char* colors, int nc,
                       int text_color, int thickness, int flags, const unsigned char* names, const int* name_len, int name_ld,
                       const unsigned char* atlas, int gh, int gw, void* stream);
+
+/*
+ * plot_images of the reference (utils/plots.py:128-203): the mosaic of the first batches that test.py / train.py save as
+ * test_batch*_labels.jpg / _pred.jpg.  Five launches build it on the device: cft_mosaic_compose (the images into the grid),
+ * cft_mosaic_slots (targets -> the slot table of cft_detect_render, which then draws every cell as one "image" with the flags
+ * CFT_RENDER_CONF1 | CFT_RENDER_SIGNED), cft_mosaic_finish (file names and cell borders) and cft_mosaic_area (the final INTER_AREA
+ * reduction).  All are asynchronous on the caller's stream, allocate nothing and do not synchronise; each pixel or slot is written by
+ * one thread and only integer atomics are used: every result is the same run to run.  Arguments are checked on the host first;
+ * nothing is launched on CFT_EINVAL.  cv2's float resize, anti-aliased lines and Hershey font are not reproduced ("parity with cv2
+ * unpinned"); the raster below is this project's definition.
+ *
+ * Geometry (host, Python doubles, :142-152): bs = min(B, max_subplots), ns = ceil(sqrt(bs)), sf = max_size / max(H, W), with sf < 1
+ * h = ceil(sf * H), w = ceil(sf * W), else h = H, w = W.  Cell i sits at block_x = w * (i / ns), block_y = h * (i % ns) (column-major).
+ *
+ * cft_mosaic_compose writes the HWC uint8 mosaic [ns*h, ns*w, 3] (row stride mstride bytes) of one stream from channels [c0, c0 + 3) of
+ * the [B, C, H, W] batch img (dtype CFT_MOSAIC_U8 / F16 / F32; sb, sc, sh, sw = element strides, so a channel slice is a legal input).
+ *   value   every element as float32, times 255 when the maximum of image 0 over all C channels is <= 1 (:137-138; the maximum is
+ *           found on the device by a reduction launch in front, in maxkey [1] (device, 4 bytes, overwritten); a NaN counts as > 1),
+ *           resized when resize != 0, clamped to [0, 255] (NaN: 0) and truncated toward zero;
+ *   resize  float32 bilinear in OpenCV's published float convention: scale = 1 / (dst / src) in double, source coordinate
+ *           f = (float)((d + 0.5) * scale - 0.5), s = floor(f), fraction a1 = f - s and a0 = 1 - a1 in float32, the indices s and s + 1
+ *           clamped to the image (the fractions are kept); horizontal pass a0 * p0 + a1 * p1 on both rows, then vertical
+ *           b0 * r0 + b1 * r1, every operation one float32 rounding (no fused multiply-add).  resize == 0 needs h == H and w == W;
+ *   cells   without an image (i >= bs) are 255.
+ *
+ * cft_mosaic_slots fills slots [bs, cap, 16] int32 (words 0..3 x1 y1 x2 y2 relative to the cell, 4 cls, 5 tenths of the confidence,
+ * 6 valid; the rest 0; 16-byte aligned), from one of two target forms:
+ *   rows   [nt, cols] float32 (f64 == 0) or float64 (f64 != 0), cols 6 = image, class, x, y, w, h (labels) or 7 = the same and conf;
+ *          a row belongs to image i when its first value equals i exactly; rows of other images are ignored;
+ *   dets   (rows NULL) [B, max_det, 6] float32 xyxy conf cls with counts [B], the cft_nms output: output_to_target (:119-125) fused in,
+ *          xyxy2xywh in float32, then the row treatment in float64.
+ * Per image, in the rows' dtype with one rounding per operation (:166-179): xywh2xyxy; if the image has boxes and the maximum over
+ * the four coordinates of all its boxes is <= 1.01 (the constant rounded to the dtype; a NaN is not), x * w and y * h; otherwise, if
+ * *sf < 1, every coordinate * sf (sf: HOST double, rounded to the dtype); then int(), truncation toward zero.  Labels are always drawn, rows
+ * with a confidence only if conf > 0.25.  The drawn targets of an image fill its slots in REVERSE order (the reference draws target j
+ * after j - 1, cft_detect_render puts the lowest slot on top).  Word 5 = the digits of '%.1f' % conf: tenths 0..10, correctly rounded,
+ * ties to even on the exact binary value, in integers (above 1: 10; negative or NaN: 0).  A class (truncated toward zero) outside [0, nc)
+ * is skipped and ORs CFT_MOSAIC_BAD_CLASS into flag [1] (device int); more drawn targets than cap in one cell ORs CFT_MOSAIC_OVERFLOW
+ * (the slots then hold the last cap drawn targets of that image).
+ *
+ * cft_mosaic_finish, after the boxes, one launch over both mosaics (img_ir may be NULL): the file name of cell i (codes [bs, 40]
+ * uint8, name_len [bs] int clamped to [0, 40]; codes NULL: no text) from the glyph atlas with its top-left at (block_x + 5,
+ * block_y + 5), magnification 1, colour (220, 220, 220) where the atlas value is >= 128, a code outside 32..127 as a space, clipped
+ * to the cell; then the cell border of every occupied cell, white: the pixels of [block_x - 1, block_x + w + 1] x [block_y - 1,
+ * block_y + h + 1] that are not inside [block_x + 2, block_x + w - 2] x [block_y + 2, block_y + h - 2] (the hard-edged form of
+ * cv2.rectangle(..., thickness=3)), clipped to the mosaic.  Border over text over boxes.
+ *
+ * cft_mosaic_area: HWC uint8 3-channel INTER_AREA reduction [sh, sw] -> [dh, dw], the CFT_PAIR_AREA arithmetic bit for bit (equal
+ * sizes: a copy); at most CFT_PAIR_MAX_REDUCTION per axis.  src and dst must not overlap.
+ */
+enum { CFT_MOSAIC_U8 = 0, CFT_MOSAIC_F16 = 1, CFT_MOSAIC_F32 = 2 };
+#define CFT_MOSAIC_BAD_CLASS 1
+#define CFT_MOSAIC_OVERFLOW 2
+#define CFT_MOSAIC_NAME_CHARS 40
+int cft_mosaic_compose(const void* img, int dtype, int B, int C, int H, int W, long sb, long sc, long sh, long sw, int c0, int bs, int ns,
+                       int h, int w, int resize, unsigned char* mosaic, long mstride, int* maxkey, void* stream);
+int cft_mosaic_slots(const void* rows, int nt, int cols, int f64, const float* dets, const int* counts, int B, int max_det, int bs, int cap,
+                     int nc, int h, int w, const double* sf, int* slots, int* flag, void* stream);
+int cft_mosaic_finish(unsigned char* img_rgb, unsigned char* img_ir, long stride_rgb, long stride_ir, int bs, int ns, int h, int w,
+                      const unsigned char* codes, const int* name_len, const unsigned char* atlas, int gh, int gw, void* stream);
+int cft_mosaic_area(const unsigned char* src, long src_stride, int sh, int sw, unsigned char* dst, long dst_stride, int dh, int dw,
+                    void* stream);
 
 /*
  * ComputeLoss of the reference (utils/loss.py:88-216) and its gradient with respect to the head outputs.

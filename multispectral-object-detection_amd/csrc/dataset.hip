@@ -21,34 +21,7 @@
 #define PAIR_LDS_BUDGET (64 * 1024)    // bytes of source span per workgroup: two workgroups per CU at the worst, a 4 x 256 tile reduced 4x
 // CFT_PAIR_MAX_REDUCTION (cft_hip.h): INTER_AREA source pixels per output pixel and axis; what a tile's span in LDS admits, and it bounds the fp32 error (see below)
 
-// One axis of computeResizeAreaTab for output index d: source cells [c0, c0 + n) with weight w_first for the first, w_last for the
-// last and w_mid between (n == 1: w_first).  Cell boundaries d * ssize / dsize are exact in integers; the covered fractions and
-// cv2's 1e-3 cut-off for a sliver of a cell are evaluated in double, the weights are float as cv2's DecimateAlpha.
-struct AreaTab { int c0, n; float w_first, w_mid, w_last; };
-
-__device__ __forceinline__ AreaTab area_tab(int d, int ssize, int dsize) {
-  const double scale = (double)ssize / (double)dsize;
-  const long lo = (long)d * ssize, hi = (long)(d + 1) * ssize;         // fsx1 = lo / dsize, fsx2 = hi / dsize
-  int s1 = (int)((lo + dsize - 1) / dsize);                            // ceil(fsx1)
-  int s2 = (int)(hi / dsize);                                          // floor(fsx2)
-  s2 = s2 < ssize - 1 ? s2 : ssize - 1;
-  s1 = s1 < s2 ? s1 : s2;
-  const double cell = scale < (double)ssize - (double)lo / dsize ? scale : (double)ssize - (double)lo / dsize;
-  const double head = (double)((long)s1 * dsize - lo) / dsize;         // s1 - fsx1
-  const double tail = (double)(hi - (long)s2 * dsize) / dsize;         // fsx2 - s2
-  const bool has_head = head > 1e-3, has_tail = tail > 1e-3;
-  const float wh = (float)(head / cell), wm = (float)(1.0 / cell);
-  const double t1 = tail < 1.0 ? tail : 1.0;
-  const float wt = (float)((t1 < cell ? t1 : cell) / cell);
-  AreaTab t;
-  t.c0 = has_head ? s1 - 1 : s1;
-  t.n = (has_head ? 1 : 0) + (s2 - s1) + (has_tail ? 1 : 0);
-  t.w_mid = wm;
-  t.w_first = has_head ? wh : (s2 > s1 ? wm : wt);
-  t.w_last = has_tail ? wt : (s2 > s1 ? wm : wh);
-  return t;
-}
-__device__ __forceinline__ float area_weight(const AreaTab& t, int i) { return i == 0 ? t.w_first : (i == t.n - 1 ? t.w_last : t.w_mid); }
+// AreaTab / area_tab / area_weight (one axis of computeResizeAreaTab) are in resize_common.h, shared with cft_mosaic_area.
 
 // The source span [s0, s1) that the output range [r0, r1) of one axis reads.
 __device__ __forceinline__ void source_span(int mode, int r0, int r1, int ssize, int dsize, bool rows, int& s0, int& s1) {

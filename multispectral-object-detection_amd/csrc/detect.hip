@@ -106,6 +106,9 @@ struct RenderArgs {
   int max_det, nc, text_color, t, flags, name_ld, gh, gw;
 };
 
+// characters of the confidence suffix: ' d.dd', or ' d.d' with CFT_RENDER_CONF1
+__device__ __forceinline__ int render_conf_chars(int flags) { return (flags & CFT_RENDER_CONF1) ? 4 : 5; }
+
 // What the raster needs of one slot: the box, class, hundredths and the label's length in characters (0: no label).
 struct RenderBox { int x1, y1, x2, y2, cls, hund, n, pad; };
 
@@ -113,15 +116,16 @@ __device__ __forceinline__ bool load_render_box(const RenderArgs& a, const int* 
   const int4 p = *reinterpret_cast<const int4*>(slot);
   const int4 q = *reinterpret_cast<const int4*>(slot + 4);
   if (q.z == 0 || q.x < 0 || q.x >= a.nc) return false;
-  e.x1 = clampi(p.x, 0, RENDER_MAX_COORD); e.y1 = clampi(p.y, 0, RENDER_MAX_COORD);
-  e.x2 = clampi(p.z, 0, RENDER_MAX_COORD); e.y2 = clampi(p.w, 0, RENDER_MAX_COORD);
+  const int lo = (a.flags & CFT_RENDER_SIGNED) ? -RENDER_MAX_COORD : 0;
+  e.x1 = clampi(p.x, lo, RENDER_MAX_COORD); e.y1 = clampi(p.y, lo, RENDER_MAX_COORD);
+  e.x2 = clampi(p.z, lo, RENDER_MAX_COORD); e.y2 = clampi(p.w, lo, RENDER_MAX_COORD);
   e.cls = q.x;
-  e.hund = clampi(q.y, 0, 100);
+  e.hund = clampi(q.y, 0, (a.flags & CFT_RENDER_CONF1) ? 10 : 100);      // tenths with CFT_RENDER_CONF1
   e.n = 0;
   e.pad = 0;
   if (a.flags & CFT_RENDER_LABELS) {
     e.n = clampi(a.name_len[q.x], 0, a.name_ld);
-    if (a.flags & CFT_RENDER_CONF) e.n += 5;        // ' d.dd'
+    if (a.flags & CFT_RENDER_CONF) e.n += render_conf_chars(a.flags);
   }
   return true;
 }
@@ -144,10 +148,13 @@ __device__ __forceinline__ int render_cover(const RenderArgs& a, const RenderBox
     const int top = e.y1 - 1 - chh, dx = px - e.x1, dy = py - top;
     if (dy >= 0 && dy < chh && dx < e.n * cw) {
       const int k = dx / cw, u = (dx - k * cw) / m, v = dy / m;
-      const int len = e.n - ((a.flags & CFT_RENDER_CONF) ? 5 : 0);
+      const int len = e.n - ((a.flags & CFT_RENDER_CONF) ? render_conf_chars(a.flags) : 0);
       int code;
       if (k < len) {
         code = a.names[(long)e.cls * a.name_ld + k];
+      } else if (a.flags & CFT_RENDER_CONF1) {
+        const int j = k - len;
+        code = j == 0 ? ' ' : (j == 1 ? '0' + e.hund / 10 : (j == 2 ? '.' : '0' + e.hund % 10));
       } else {
         const int j = k - len;
         code = j == 0 ? ' ' : (j == 1 ? '0' + e.hund / 100 : (j == 2 ? '.' : (j == 3 ? '0' + (e.hund / 10) % 10 : '0' + e.hund % 10)));
@@ -235,8 +242,9 @@ extern "C" int cft_detect_render(const void* desc_dev, const void* desc_host, in
   CFT_REQUIRE(((size_t)boxes & 15) == 0, "cft_detect_render: boxes must be 16-byte aligned");
   CFT_REQUIRE(nc >= 1 && nc <= 32767, "cft_detect_render: nc must be in [1, 32767]");
   CFT_REQUIRE(thickness >= 1 && thickness <= 64, "cft_detect_render: thickness must be in [1, 64]");
-  CFT_REQUIRE((flags & ~(CFT_RENDER_LABELS | CFT_RENDER_CONF)) == 0, "cft_detect_render: unknown flag");
+  CFT_REQUIRE((flags & ~(CFT_RENDER_LABELS | CFT_RENDER_CONF | CFT_RENDER_CONF1 | CFT_RENDER_SIGNED)) == 0, "cft_detect_render: unknown flag");
   CFT_REQUIRE(!(flags & CFT_RENDER_CONF) || (flags & CFT_RENDER_LABELS), "cft_detect_render: the conf flag needs the labels flag");
+  CFT_REQUIRE(!(flags & CFT_RENDER_CONF1) || (flags & CFT_RENDER_CONF), "cft_detect_render: the tenths flag needs the conf flag");
   CFT_REQUIRE(text_color >= 0 && text_color <= 0xffffff, "cft_detect_render: text colour is three bytes");
   if (flags & CFT_RENDER_LABELS) {
     CFT_REQUIRE(names && name_len && atlas, "cft_detect_render: labels need names, name_len and atlas");

@@ -21,10 +21,16 @@ The rest of what ``python test.py`` gives is behind keywords that are off by def
 * ``save_json``    the COCO-style list of test.py:173-182, returned as ``jdict`` and, with a ``save_dir``, written to
                    ``save_dir/predictions.json``.
 
+* ``plots``        the batch mosaics of test.py's ``plots=True`` (:220-225): for the first three batches
+                   ``save_dir/test_batch{i}_labels.jpg`` and ``test_batch{i}_pred.jpg`` (``utils.plots.plot_images``, built on the
+                   device) with their ``_ir`` twins for the second stream, twelve files.  The PR / F1 curve images and the
+                   confusion-matrix image of ``plots=True`` are not drawn.
+
 The values written come from one kernel (``cft_eval_export``) and one device-to-host copy per batch: the only added
-synchronisation, and only when a save option is on.  PR / F1 curve plots, wandb logging and pycocotools scoring are not done.
+synchronisation, and only when a save option is on.  wandb logging and pycocotools scoring are not done.
 """
 import json
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import torch
@@ -56,8 +62,30 @@ def _apriori_rows(targets, B, no, H, W):
     return extra
 
 
+def _save_mosaics(host, event, flag, files):
+    """Pool job of ``plots``: wait for the batch's device-to-host copies, check the slot kernel's flag word, encode."""
+    from .utils.plots import check_mosaic_flag, save_mosaic
+    event.synchronize()
+    if flag is not None:
+        check_mosaic_flag(int(flag[0]))
+    for a, f in zip(host, files):
+        save_mosaic(a.numpy(), f)
+
+
+def _plot_batch(pool, img, targets, paths, fname, names):
+    """One mosaic (both streams) on the device, then its copies to pinned memory; the wait and the encoding go to the pool."""
+    from .utils.plots import mosaic_file_names, plot_images_device
+    mosaics, flag, _ = plot_images_device(img, targets, paths, names)
+    host = [torch.empty(m.shape, dtype=m.dtype).pin_memory().copy_(m, non_blocking=True) for m in mosaics]
+    if flag is not None:
+        flag = torch.empty(1, dtype=torch.int32).pin_memory().copy_(flag, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    return pool.submit(_save_mosaics, host, event, flag, mosaic_file_names(fname, len(host)))
+
+
 def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None, confusion=False,
-             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None):
+             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None, plots=False, names=None):
     """batches: an iterable of ``(img6_uint8 [B, 6, H, W], targets [nt, 6], paths, shapes)`` as test.py's dataloader yields.
     Returns test.py's ``((mp, mr, map50, map75, map), maps)``; with ``compute_loss``, test.py's
     ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches.
@@ -65,8 +93,13 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
     With any of ``confusion``, ``save_txt``, ``save_hybrid``, ``save_json`` (module docstring) a third element follows:
     ``{"confusion_matrix": (nc+1, nc+1) float64 numpy array or None, "jdict": list of entries or None}``.
 
+    ``plots`` (needs a ``save_dir``): the label and prediction mosaics of the first three batches, both streams (module docstring), with
+    the class ``names`` (None: class numbers); the files are complete when this returns.  It adds no element to the return value.
+
     ``details``: a dict that receives ``"result"``, the ``EvalResult`` behind the returned tuple (per-class p / r / ap, nt, seen - what
     test.py's table prints, tools/val.py); the return value does not change."""
+    if plots and save_dir is None:
+        raise ValueError("evaluate: plots needs a save_dir")
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model must be on the GPU (this package has no CPU path)")
@@ -76,6 +109,9 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
         if save_dir is None:
             raise ValueError("evaluate: save_txt / save_hybrid need a save_dir")
         (Path(save_dir) / 'labels').mkdir(parents=True, exist_ok=True)    # test.py:54
+    if plots:
+        Path(save_dir).mkdir(parents=True, exist_ok=True)
+    pool, jobs = (ThreadPoolExecutor(max_workers=4), []) if plots else (None, [])
     jdict = [] if save_json else None
     ev = DetectionEvaluator(1 if single_cls else nc, single_cls, confusion=confusion)          # test.py:74, :97
     loss = torch.zeros(3, device=device) if compute_loss is not None else None
@@ -97,6 +133,13 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
                     out = torch.cat((out.float(), extra.pin_memory().to(device, non_blocking=True)), 1)
             dets, counts = batched_nms(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
         ev.update(dets, counts, targets, (H, W), shapes)
+        if plots and nb < 3:                                               # test.py:220-225
+            jobs.append(_plot_batch(pool, img, targets, paths, Path(save_dir) / f'test_batch{nb}_labels.jpg', names))
+            pd = dets
+            if single_cls:                                                 # test.py:146-147 zeroes the class in place before it plots `out`
+                pd = dets.clone()
+                pd[..., 5] = 0
+            jobs.append(_plot_batch(pool, img, (pd, counts), paths, Path(save_dir) / f'test_batch{nb}_pred.jpg', names))
         if save_txt or save_json:
             for stem, rows in export_rows(export_batch(dets, counts, (H, W), shapes, single_cls), paths):
                 if save_txt:
@@ -105,6 +148,10 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
                 if save_json:
                     jdict.extend(json_entry(stem, r[5], r[12:16], r[4]) for r in rows)
         nb += 1
+    if pool is not None:
+        pool.shutdown(wait=True)                                           # no thread outlives the call: the files are complete
+        for j in jobs:
+            j.result()
     res = ev.compute()
     if details is not None:
         details["result"] = res

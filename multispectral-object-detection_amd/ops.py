@@ -786,6 +786,102 @@ def detect_render(desc_dev, desc_host, boxes, colors, text_color, thickness, fla
     _lib.check(st, "cft_detect_render")
 
 
+_MOSAIC_DTYPES = {torch.uint8: "CFT_MOSAIC_U8", torch.float16: "CFT_MOSAIC_F16", torch.float32: "CFT_MOSAIC_F32"}
+
+
+def _hwc_u8(t, what):
+    _require_cuda(t, what)
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.stride(2) != 1 or t.stride(1) != 3:
+        raise ValueError(f"{what}: a mosaic must be an HWC uint8 CUDA tensor with contiguous pixels")
+
+
+def mosaic_compose(images, c0, bs, ns, h, w, resize, out, maxkey=None):
+    """cft_mosaic_compose: channels [c0, c0 + 3) of the first ``bs`` images of the (possibly strided) ``[B, C, H, W]`` uint8 / fp16 / fp32
+    batch into the HWC uint8 mosaic ``out`` [ns*h, ns*w, 3].  ``maxkey`` int32 [1]: device scratch for the maximum of image 0."""
+    _require_cuda(images, "mosaic_compose")
+    _hwc_u8(out, "mosaic_compose")
+    if images.dim() != 4 or images.dtype not in _MOSAIC_DTYPES:
+        raise ValueError(f"mosaic_compose: images must be a [B, C, H, W] uint8, float16 or float32 tensor, got {images.dtype} {tuple(images.shape)}")
+    if tuple(out.shape) != (ns * h, ns * w, 3):
+        raise ValueError(f"mosaic_compose: out must be [{ns * h}, {ns * w}, 3], got {tuple(out.shape)}")
+    if maxkey is None:
+        maxkey = torch.empty((1,), dtype=torch.int32, device=images.device)
+    B, C, H, W = images.shape
+    st = _lib.load().cft_mosaic_compose(images.data_ptr(), _lib._consts[_MOSAIC_DTYPES[images.dtype]], B, C, H, W, *images.stride(), int(c0), int(bs),
+                                        int(ns), int(h), int(w), int(bool(resize)), out.data_ptr(), out.stride(0), maxkey.data_ptr(), _stream())
+    _lib.check(st, "cft_mosaic_compose")
+    return out
+
+
+def mosaic_slots(targets, bs, cap, nc, h, w, sf, flag=None):
+    """cft_mosaic_slots: ``targets`` is a contiguous float32 / float64 ``[nt, 6 or 7]`` CUDA tensor (image, class, x, y, w, h[, conf]) or the
+    ``(dets [B, max_det, 6] float32, counts [B] int32)`` pair of ``batched_nms``.  Returns ``(slots int32 [bs, cap, 16], flag int32 [1])``
+    on the device; ``flag`` is ORed into (CFT_MOSAIC_BAD_CLASS, CFT_MOSAIC_OVERFLOW)."""
+    import ctypes
+    pair = isinstance(targets, (tuple, list))
+    first = targets[0] if pair else targets
+    _require_cuda(first, "mosaic_slots")
+    slots = torch.empty((int(bs), int(cap), BOX_WORDS), dtype=torch.int32, device=first.device)
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=first.device)
+    sfd = ctypes.c_double(float(sf))
+    if pair:
+        dets, counts = targets
+        _require_cuda(counts, "mosaic_slots")
+        if dets.dtype != torch.float32 or dets.dim() != 3 or dets.shape[2] != 6 or not dets.is_contiguous() or dets.shape[1] == 0:
+            raise ValueError(f"mosaic_slots: dets must be a contiguous float32 [B, max_det, 6] tensor, got {dets.dtype} {tuple(dets.shape)}")
+        if counts.dtype != torch.int32 or tuple(counts.shape) != (dets.shape[0],) or not counts.is_contiguous():
+            raise ValueError(f"mosaic_slots: counts must be a contiguous int32 [{dets.shape[0]}] tensor")
+        args = (None, 0, 7, 1, dets.data_ptr(), counts.data_ptr(), dets.shape[0], dets.shape[1])
+    else:
+        t = targets
+        if t.dtype not in (torch.float32, torch.float64) or t.dim() != 2 or t.shape[1] not in (6, 7) or not t.is_contiguous() or t.shape[0] == 0:
+            raise ValueError(f"mosaic_slots: rows must be a contiguous float32 / float64 [nt > 0, 6 or 7] tensor, got {t.dtype} {tuple(t.shape)}")
+        args = (t.data_ptr(), t.shape[0], t.shape[1], int(t.dtype == torch.float64), None, None, 0, 0)
+    st = _lib.load().cft_mosaic_slots(*args, int(bs), int(cap), int(nc), int(h), int(w), ctypes.byref(sfd), slots.data_ptr(), flag.data_ptr(), _stream())
+    _lib.check(st, "cft_mosaic_slots")
+    return slots, flag
+
+
+def mosaic_finish(mosaic, mosaic_ir, bs, ns, h, w, codes=None, name_len=None, atlas=None):
+    """cft_mosaic_finish: file names (``codes`` uint8 [bs, 40], ``name_len`` int32 [bs], ``atlas`` uint8 [96, gh, gw]; None: no text) and the
+    white cell borders into one or two mosaics, in place, one launch."""
+    gh = gw = 0
+    for m in (mosaic,) if mosaic_ir is None else (mosaic, mosaic_ir):
+        _hwc_u8(m, "mosaic_finish")
+        if tuple(m.shape) != (ns * h, ns * w, 3):
+            raise ValueError(f"mosaic_finish: a mosaic must be [{ns * h}, {ns * w}, 3], got {tuple(m.shape)}")
+    if codes is not None:
+        nch = _lib._consts["CFT_MOSAIC_NAME_CHARS"]
+        if codes.dtype != torch.uint8 or tuple(codes.shape) != (bs, nch) or not codes.is_contiguous():
+            raise ValueError(f"mosaic_finish: codes must be a contiguous uint8 [{bs}, {nch}] tensor")
+        if name_len is None or name_len.dtype != torch.int32 or tuple(name_len.shape) != (bs,) or not name_len.is_contiguous():
+            raise ValueError(f"mosaic_finish: name_len must be a contiguous int32 [{bs}] tensor")
+        if atlas is None or atlas.dtype != torch.uint8 or atlas.dim() != 3 or atlas.shape[0] != 96 or not atlas.is_contiguous():
+            raise ValueError("mosaic_finish: atlas must be a contiguous uint8 [96, gh, gw] tensor")
+        for t in (codes, name_len, atlas):
+            _require_cuda(t, "mosaic_finish")
+        gh, gw = atlas.shape[1], atlas.shape[2]
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    st = _lib.load().cft_mosaic_finish(mosaic.data_ptr(), ptr(mosaic_ir), mosaic.stride(0), mosaic_ir.stride(0) if mosaic_ir is not None else 0, int(bs),
+                                       int(ns), int(h), int(w), ptr(codes), ptr(name_len) if codes is not None else None,
+                                       ptr(atlas) if codes is not None else None, gh, gw, _stream())
+    _lib.check(st, "cft_mosaic_finish")
+
+
+def mosaic_area(src, dh, dw):
+    """cft_mosaic_area: the INTER_AREA reduction of an HWC uint8 mosaic to ``[dh, dw, 3]`` (a new tensor), at most 4x per axis."""
+    _hwc_u8(src, "mosaic_area")
+    sh, sw = src.shape[0], src.shape[1]
+    r = _lib._consts["CFT_PAIR_MAX_REDUCTION"]
+    if not (0 < dh <= sh and 0 < dw <= sw and dh * r >= sh and dw * r >= sw):
+        raise ValueError(f"mosaic_area: {sh}x{sw} -> {dh}x{dw} is not a reduction by 1x to {r}x per axis")
+    dst = torch.empty((int(dh), int(dw), 3), dtype=torch.uint8, device=src.device)
+    st = _lib.load().cft_mosaic_area(src.data_ptr(), src.stride(0), sh, sw, dst.data_ptr(), dst.stride(0), int(dh), int(dw), _stream())
+    _lib.check(st, "cft_mosaic_area")
+    return dst
+
+
 # ------------------------------------------------------------------------------ training-mode forward
 _dropout_state = {"seed": 0x5EED, "calls": 0}
 

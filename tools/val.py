@@ -1,6 +1,6 @@
 """Validate a checkpoint on a paired RGB + IR dataset on disk: the command-line form of the reference's test.py.
 
-    python tools/val.py DATA.yaml WEIGHTS.pt [--img-size 640] [--batch-size 32] [--single-cls] [--save-txt] [--save-json] [--verbose]
+    python tools/val.py DATA.yaml WEIGHTS.pt [--img-size 640] [--batch-size 32] [--single-cls] [--save-txt] [--save-json] [--plots] [--verbose]
 
 DATA.yaml holds ``val_rgb`` and ``val_ir`` (directories or *.txt lists; relative paths are taken from the yaml's directory), ``nc``
 and ``names``.  The loader is built as test.py builds it (:86-94: ``rect=True, pad=0.5``, the model's largest stride), every batch is
@@ -34,6 +34,7 @@ def main(argv=None):
     ap.add_argument("--single-cls", action="store_true")
     ap.add_argument("--save-txt", action="store_true")
     ap.add_argument("--save-json", action="store_true")
+    ap.add_argument("--plots", action="store_true", help="test_batch{0,1,2}_{labels,pred}[_ir].jpg of the first three batches in --save-dir")
     ap.add_argument("--save-dir", default="runs/val")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--verbose", action="store_true")
@@ -71,7 +72,8 @@ def main(argv=None):
                          f"fix the labels or nc, or pass --single-cls")
     details = {}
     evaluate(model, loader, nc, conf_thres=opt.conf_thres, iou_thres=opt.iou_thres, single_cls=opt.single_cls, save_txt=opt.save_txt,
-             save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json) else None, details=details)
+             save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json or opt.plots) else None, details=details,
+             plots=opt.plots, names=names if opt.plots else None)
     res = details["result"]
 
     print(('%20s' + '%12s' * 7) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.75', 'mAP@.5:.95'))
@@ -81,7 +83,7 @@ def main(argv=None):
         ap = res.ap
         for i, c in enumerate(res.ap_class):
             print(pf % (names[c] if c < len(names) else str(c), res.seen, res.nt[c], res.p[i], res.r[i], ap[i, 0], ap[i, 5], ap[i].mean()))
-    if opt.save_txt or opt.save_json:
+    if opt.save_txt or opt.save_json or opt.plots:
         print(f"Results saved to {opt.save_dir}")
     return res
 
