@@ -654,20 +654,48 @@ int cft_anchor_evolve(const float* wh, long n, int na, float thr, const double* 
  *
  * cft_ema_update: e <- fma(one_minus_d, m, d * e) over every segment (e = the EMA tensor, m = the model's); d and one_minus_d are
  * each computed in double by the caller and rounded to float, as `v *= d; v += (1. - d) * msd[k]` does with Python scalars.
+ *
+ * cft_adam_step: torch.optim.Adam / AdamW (train.py:558 `optim.Adam(pg0, lr=hyp['lr0'], betas=(hyp['momentum'], 0.999))`) with
+ * amsgrad = False and maximize = False, on the same table layout (cft_adam_seg_t rows, then the canonical work rows) with the same
+ * chunk / max_blocks / grad_scale / found_inf / stream arguments.  hyper_host: HOST double [ngroups][6] = lr, beta1, beta2, eps,
+ * weight_decay, decoupled (0 = Adam's L2 term, 1 = AdamW's decay) of each param group; lr, eps, weight_decay >= 0, 0 <= beta < 1.
+ * step: DEVICE float [1] per segment, the number of steps this tensor has taken; it stays on the device because only the device
+ * knows whether found_inf skipped a step.  coef: DEVICE float [nseg][2] scratch, 8-byte aligned, written and read by this call only.
+ * Two launches on the stream, the second reading what the first wrote:
+ *   adam_prepare_kernel, one thread per segment: unless *found_inf != 0, s = *step + 1; *step = s; in double
+ *     bc1 = 1 - pow(beta1, s), bc2 = 1 - pow(beta2, s); coef[seg] = {(float)(lr / bc1), (float)sqrt(bc2)} = {step_size, bc2_sqrt},
+ *     what torch's single-tensor path computes with Python floats;
+ *   adam_step_kernel, over the work rows as cft_sgd_step.  The float constants of a group are formed on the host from the doubles:
+ *     w1 = (float)(1 - beta1), b2 = (float)beta2, w2 = (float)(1 - beta2), eps, wd, decay = (float)(1 - lr * wd).
+ * Rounding rule, per element (floating-point contraction is off: an fma is where the rule says fma and nowhere else; sqrtf and /
+ * are correctly rounded, the build has no fast-math flag):
+ *   g0  = grad_scale ? g * (float)(1.0 / (double)*grad_scale) : g
+ *   Adam  (L2), wd != 0:        g1 = fma(wd, p, g0);  p0 = p
+ *   AdamW (decoupled), wd != 0: p0 = p * decay;       g1 = g0
+ *   m1  = fma(w1, g1 - m, m)
+ *   v1  = fma(w2 * g1, g1, b2 * v)
+ *   den = sqrtf(v1) / bc2_sqrt + eps
+ *   p  <- p0 + (-step_size * m1) / den;   m <- m1;   v <- v1
+ * which is the order of operations of torch's single-tensor Adam (lerp_, mul_().addcmul_(), addcdiv_).  m and v start as zeros.
+ * With found_inf given and *found_inf != 0 nothing is written, the step counters included.
  */
 #define CFT_OPTIM_CHUNK 4096
 #define CFT_OPTIM_MAX_BLOCKS 2048
 #define CFT_OPTIM_MAX_GROUPS 8
 #define CFT_SGD_SEG_BYTES 40
 #define CFT_EMA_SEG_BYTES 24
+#define CFT_ADAM_SEG_BYTES 56
 #define CFT_OPTIM_WORK_BYTES 16
 typedef struct { float* p; const float* g; float* buf; long n; long group; } cft_sgd_seg_t;
 typedef struct { float* e; const float* m; long n; } cft_ema_seg_t;
+typedef struct { float* p; const float* g; float* m; float* v; float* step; long n; long group; } cft_adam_seg_t;
 typedef struct { int seg; int pad; long start; } cft_optim_work_t;
 int cft_sgd_step(const void* table_dev, const void* table_host, int nseg, long nwork, int chunk, int max_blocks,
                  const float* hyper_host, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
 int cft_ema_update(const void* table_dev, const void* table_host, int nseg, long nwork, int chunk, int max_blocks,
                    float d, float one_minus_d, void* stream);
+int cft_adam_step(const void* table_dev, const void* table_host, int nseg, long nwork, int chunk, int max_blocks,
+                  const double* hyper_host, int ngroups, float* coef, const float* grad_scale, const float* found_inf, void* stream);
 
 #ifdef __cplusplus
 }
