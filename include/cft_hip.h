@@ -228,6 +228,68 @@ typedef struct {
 } cft_pair_desc_t;
 int cft_pair_batch_u8(const void* desc_dev, const void* desc_host, int B, unsigned char* dst, int dst_h, int dst_w, int color, void* stream);
 
+/*
+ * One launch writes the whole uint8 [B, 6, dst_h, dst_w] batch of the AUGMENTED RGB + IR training loader (RGB in planes 0-2, IR in
+ * planes 3-5): per item everything between the decoded originals and torch.from_numpy(img_all) of the reference's __getitem__ with
+ * augment=True (utils/datasets.py:1155-1281) - the load_image_rgb_ir resize (INTER_LINEAR in both directions), the 4-tile mosaic
+ * canvas of load_mosaic_RGB_IR (:1464-1603) or the grey letterbox, cv2.warpAffine of random_perspective_rgb_ir (:1819-1914),
+ * augment_hsv per stream (:1374-1385), the two flips and the packing.  Every output pixel is a gather: no canvas is materialised.
+ * The sources are HWC uint8 in RGB order (PIL); cv2 itself is absent, so "parity with cv2 unpinned": the raster below restates
+ * OpenCV's published 8-bit paths and is defined so that the numpy restatement tests/augment_ref.py gives the same bytes.
+ *
+ * The table has one cft_aug_desc_t row per output image; luts is uint8 [B, 2, 3, 256] (stream RGB / IR; hue, saturation, value).
+ * Output pixel (y, x) of image b, both streams:
+ *   1. flips: y' = flip & CFT_AUG_FLIPUD ? dst_h - 1 - y : y,  x' = flip & CFT_AUG_FLIPLR ? dst_w - 1 - x : x.
+ *   2. warp == 0: the value is canvas pixel (y', x').  warp == 1 (inv = the inverse of M[:2] that the host forms in double by
+ *      warpAffine's closed form: D = 1 / (m00 m11 - m01 m10), a00 = m11 D, a01 = -m01 D, a10 = -m10 D, a11 = m00 D,
+ *      a02 = -a00 m02 - a01 m12, a12 = -a10 m02 - a11 m12; inv = {a00, a01, a02, a10, a11, a12}):
+ *        X = (rint(a00 * x' * 1024) + rint((a01 * y' + a02) * 1024) + 16) >> 5,  Y likewise with a10, a11, a12 (doubles, one rounding
+ *        per operation, no contraction; 64-bit integers); sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31;
+ *        value = (p(sy, sx) (32-fx)(32-fy) + p(sy, sx+1) fx (32-fy) + p(sy+1, sx) (32-fx) fy + p(sy+1, sx+1) fx fy + 512) >> 10
+ *      per channel, each of the four canvas pixels p looked up on its own.
+ *   3. canvas pixel (cy, cx): 114 outside [0, canvas_h) x [0, canvas_w) and outside every tile; inside tile t (cy in [y1, y2), cx in
+ *      [x1, x2)) pixel (cy - padh, cx - padw) of the pair resized to (h, w): cv2 INTER_LINEAR for 8-bit from the (h0, w0) original,
+ *      the arithmetic of CFT_PAIR_LINEAR bit for bit; a plain read when h == h0 and w == w0.
+ *   4. HSV per stream: (r, g, b) -> 8-bit HSV: v = max, diff = v - min, s = (diff * sdiv[v] + 2048) >> 12 with sdiv[i] =
+ *      rint((255 << 12) / i), sdiv[0] = 0; hh = g - b if v == r, else b - r + 2 diff if v == g, else r - g + 4 diff;
+ *      h = (hh * hdiv[diff] + 2048) >> 12 (arithmetic shift) with hdiv[i] = rint((180 << 12) / (6 i)), hdiv[0] = 0; h += 180 if h < 0.
+ *      Then h = lut[0][h], s = lut[1][s], v = lut[2][v], and back in float32, every operation rounded once, no contraction:
+ *      sf = s / 255, vf = v / 255, hf = h / 30, k = floor(hf), f = hf - k, k = k mod 6, t0 = vf, t1 = vf (1 - sf), t2 = vf (1 - sf f),
+ *      t3 = vf (1 - sf (1 - f)); (b, g, r) = (t1,t3,t0) (t1,t0,t2) (t3,t0,t1) (t0,t2,t1) (t0,t1,t3) (t2,t1,t0) for k = 0..5;
+ *      each output is rint(255 t) (ties to even) saturated to 0..255.  s == 0 takes the same path (f drops out: all three are v).
+ *   5. planes 0-2 = r, g, b of the RGB stream, planes 3-5 of the IR stream.
+ * desc_dev / luts are device memory (what the kernel reads), desc_host the same table bytes in host memory (what the guards read:
+ * every row is checked before the launch and nothing is launched on CFT_EINVAL - pointers, sizes up to CFT_AUG_MAX_SIDE, strides,
+ * ntiles 1 or 4, warp / flip flags, finite coefficients below 2^20 in magnitude, every tile rectangle inside the canvas, its
+ * rectangle minus its pad inside [0, h) x [0, w), no two rectangles overlapping; empty rectangles are allowed).  The kernel clamps
+ * every source index it forms as well.  dst % 4 == 0 and dst_w % 4 == 0 (a thread stores 4 pixels of a plane as one dword).  No
+ * atomics: every output byte is written once by one thread.
+ */
+enum { CFT_AUG_FLIPLR = 1, CFT_AUG_FLIPUD = 2 };
+#define CFT_AUG_DESC_BYTES 400
+#define CFT_AUG_TILE_BYTES 80
+#define CFT_AUG_MAX_SIDE 16384   /* every image, canvas and output side: coordinates in 1/1024 pixel stay far inside 64 bits and the float taps exact */
+typedef struct {
+  const unsigned char* src_rgb;   /* HWC uint8 in RGB order, pixels contiguous */
+  const unsigned char* src_ir;
+  long stride_rgb, stride_ir;     /* source row strides in bytes, >= 3 * w0 */
+  int h0, w0;                     /* source size */
+  int h, w;                       /* resized size */
+  int x1, y1, x2, y2;             /* the tile's rectangle in the canvas, [x1, x2) x [y1, y2) */
+  int padw, padh;                 /* canvas (cy, cx) is resized pixel (cy - padh, cx - padw) */
+  int reserved[2];
+} cft_aug_tile_t;
+typedef struct {
+  int ntiles;                     /* 1 (letterbox) or 4 (mosaic) */
+  int warp;                       /* 0: output = canvas, 1: output = warpAffine of the canvas through inv */
+  int canvas_h, canvas_w;
+  int flip;                       /* CFT_AUG_FLIPLR | CFT_AUG_FLIPUD */
+  int reserved[3];
+  double inv[6];                  /* a00 a01 a02 a10 a11 a12 */
+  cft_aug_tile_t tile[4];
+} cft_aug_desc_t;
+int cft_augment_batch_u8(const void* desc_dev, const void* desc_host, const unsigned char* luts, int B, unsigned char* dst, int dst_h, int dst_w, void* stream);
+
 /* Elementwise out = a + b over M pixels x C channels (Add / Add2, models/common.py:228-243). */
 int cft_add(const void* a, int lda, int aoff, const void* b, int ldb, int boff,
             void* out, int ldo, int ooff, long M, int C, int dtype, void* stream);

@@ -723,6 +723,28 @@ def pair_batch_u8(desc_dev, desc_host, out, color=114):
     return out
 
 
+def augment_batch_u8(desc_dev, desc_host, luts, out):
+    """One launch assembles the augmented uint8 [B, 6, H, W] RGB + IR training batch ``out`` from a table of cft_aug_desc_t rows
+    (cft_augment_batch_u8): ``desc_dev`` [B, 400] uint8 on the device is what the kernel reads, ``desc_host`` the same bytes on the host
+    is what the guards read, ``luts`` uint8 [B, 2, 3, 256] on the device the HSV look-up tables of every image and stream."""
+    _require_cuda(out, "augment_batch_u8")
+    _require_cuda(desc_dev, "augment_batch_u8")
+    _require_cuda(luts, "augment_batch_u8")
+    B, nbytes = out.shape[0], _lib._consts["CFT_AUG_DESC_BYTES"]
+    if out.dtype != torch.uint8 or out.dim() != 4 or out.shape[1] != 6 or not out.is_contiguous():
+        raise ValueError(f"augment_batch_u8: out must be a contiguous uint8 [B, 6, H, W] tensor, got {out.dtype} {tuple(out.shape)}")
+    for t, what in ((desc_dev, "desc_dev"), (desc_host, "desc_host")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (B, nbytes) or not t.is_contiguous():
+            raise ValueError(f"augment_batch_u8: {what} must be a contiguous uint8 [{B}, {nbytes}] tensor")
+    if desc_host.is_cuda:
+        raise ValueError("augment_batch_u8: desc_host must be a host tensor")
+    if luts.dtype != torch.uint8 or tuple(luts.shape) != (B, 2, 3, 256) or not luts.is_contiguous():
+        raise ValueError(f"augment_batch_u8: luts must be a contiguous uint8 [{B}, 2, 3, 256] tensor")
+    st = _lib.load().cft_augment_batch_u8(desc_dev.data_ptr(), desc_host.data_ptr(), luts.data_ptr(), B, out.data_ptr(), out.shape[2], out.shape[3], _stream())
+    _lib.check(st, "cft_augment_batch_u8")
+    return out
+
+
 BOX_WORDS = 16        # 32-bit words per detection slot of cft_detect_boxes (include/cft_hip.h)
 
 

@@ -1,7 +1,9 @@
 """Input pre-processing that sits directly in front of the forward in every reference caller:
 ``letterbox`` of the reference's ``utils/datasets.py:1698-1728`` - resize to a stride-friendly shape keeping the
 aspect ratio, pad with grey - on the device, one kernel per image (``cft_letterbox_u8``), and the pair packer that
-builds the uint8 ``[B,6,H,W]`` batch the model consumes (``utils/datasets.py:1274-1281``: BGR->RGB, HWC->CHW)."""
+builds the uint8 ``[B,6,H,W]`` batch the model consumes (``utils/datasets.py:1274-1281``: BGR->RGB, HWC->CHW); below them the paired
+RGB + IR dataset and its loaders, validation form (one cft_pair_batch_u8 launch per batch) and augmented training form (one
+cft_augment_batch_u8 launch per batch), and the inference loaders of the detect driver."""
 import glob
 import os
 from pathlib import Path
@@ -287,18 +289,22 @@ class LoadMultiModalImagesAndLabels:  # for testing
 
             self.batch_shapes_rgb = np.ceil(np.array(shapes) * img_size / stride + pad).astype(int) * stride
 
-        # the INTER_AREA resize of cft_pair_batch_u8 reduces by at most CFT_PAIR_MAX_REDUCTION per axis: say so before any work
-        for f, (w0, h0) in zip(self.img_files_rgb, self.shapes_rgb.astype(int)):
-            r = img_size / max(h0, w0)
-            if r < 1 and (int(h0 * r) * PAIR_MAX_REDUCTION < h0 or int(w0 * r) * PAIR_MAX_REDUCTION < w0):
-                raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={img_size} would reduce it by more than {PAIR_MAX_REDUCTION}x per axis, '
-                                 f'which cft_pair_batch_u8 does not do; use a larger img_size (about {-(-max(h0, w0) // PAIR_MAX_REDUCTION)} or more) or smaller images')
+        self._check_sizes(prefix)
 
         self.imgs_rgb = [None] * n      # cache_images: the decoded originals, HWC RGB uint8 CUDA tensors
         self.imgs_ir = [None] * n
         self.labels = self.labels_rgb
         self.shapes = self.shapes_rgb
         self.indices = self.indices_rgb
+
+    def _check_sizes(self, prefix=''):
+        """The INTER_AREA resize of cft_pair_batch_u8 reduces by at most CFT_PAIR_MAX_REDUCTION per axis: say so before any work."""
+        img_size = self.img_size
+        for f, (w0, h0) in zip(self.img_files_rgb, self.shapes_rgb.astype(int)):
+            r = img_size / max(h0, w0)
+            if r < 1 and (int(h0 * r) * PAIR_MAX_REDUCTION < h0 or int(w0 * r) * PAIR_MAX_REDUCTION < w0):
+                raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={img_size} would reduce it by more than {PAIR_MAX_REDUCTION}x per axis, '
+                                 f'which cft_pair_batch_u8 does not do; use a larger img_size (about {-(-max(h0, w0) // PAIR_MAX_REDUCTION)} or more) or smaller images')
 
     def __len__(self):
         return len(self.img_files_rgb)
@@ -423,7 +429,8 @@ def _fill_sources(desc, sources):
 class _Slot:
     """One of the loader's two staging sets: pinned host bytes, their device copy, the table, and the two events that order them."""
 
-    def __init__(self):
+    def __init__(self, row_bytes=PAIR_DESC.itemsize):
+        self.row_bytes = row_bytes                 # bytes of table per batch row
         self.pinned = self.staged = self.desc_host = self.desc_dev = None
         self.ready = self.consumed = None       # upload finished (side stream) / batch assembled (consumer stream)
 
@@ -434,8 +441,8 @@ class _Slot:
             self.pinned = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
             self.staged = torch.empty(nbytes, dtype=torch.uint8, device=device)
         if self.desc_host is None or self.desc_host.shape[0] < nrows:
-            self.desc_host = torch.empty((nrows, PAIR_DESC.itemsize), dtype=torch.uint8).pin_memory()
-            self.desc_dev = torch.empty((nrows, PAIR_DESC.itemsize), dtype=torch.uint8, device=device)
+            self.desc_host = torch.empty((nrows, self.row_bytes), dtype=torch.uint8).pin_memory()
+            self.desc_dev = torch.empty((nrows, self.row_bytes), dtype=torch.uint8, device=device)
 
 
 class PairLoader:
@@ -465,6 +472,37 @@ class PairLoader:
     def batch_indices(self, b):
         return list(range(b * self.batch_size, min((b + 1) * self.batch_size, len(self.dataset))))
 
+    def _upload(self, indices, nrows, slot, pool):
+        """The originals of the pairs ``indices`` (distinct) as HWC RGB uint8 CUDA tensors, ``{index: (rgb, ir)}``: cached ones as they
+        are, the others decoded on the pool, packed into the slot's pinned bytes and uploaded without blocking (current = side stream).
+        Also sizes the slot's table for ``nrows`` rows.  Returns ``(staged, by_index)``, ``staged`` the device buffer of this upload or None."""
+        ds = self.dataset
+        by_index = {i: (ds.imgs_rgb[i], ds.imgs_ir[i]) for i in indices if ds.imgs_rgb[i] is not None}
+        missing = [i for i in indices if i not in by_index]
+        if not missing:
+            slot.reserve(0, nrows, self.device)
+            return None, by_index
+        pairs = list(pool.map(ds.load_pair, missing))
+        offs, total = [], 0
+        for rgb, ir in pairs:
+            offs.append((total, total + _align16(rgb.nbytes)))
+            total += _align16(rgb.nbytes) + _align16(ir.nbytes)
+        slot.reserve(total, nrows, self.device)
+        if ds.cache_images:                      # these bytes stay: the batch's originals live in a buffer of their own
+            staged = torch.empty(total, dtype=torch.uint8, device=self.device)
+        else:
+            staged = slot.staged
+        host = slot.pinned.numpy()
+        for (o_rgb, o_ir), (rgb, ir) in zip(offs, pairs):
+            host[o_rgb:o_rgb + rgb.nbytes] = rgb.reshape(-1)
+            host[o_ir:o_ir + ir.nbytes] = ir.reshape(-1)
+        staged[:total].copy_(slot.pinned[:total], non_blocking=True)
+        for i, (o_rgb, o_ir), (rgb, ir) in zip(missing, offs, pairs):
+            by_index[i] = (staged[o_rgb:o_rgb + rgb.nbytes].view(rgb.shape), staged[o_ir:o_ir + ir.nbytes].view(ir.shape))
+            if ds.cache_images:
+                ds.imgs_rgb[i], ds.imgs_ir[i] = by_index[i]
+        return staged, by_index
+
     def _stage(self, b, slot, pool):
         """Decode and upload batch ``b`` (side stream); returns what ``_assemble`` needs."""
         ds, indices = self.dataset, self.batch_indices(b)
@@ -474,40 +512,14 @@ class PairLoader:
             desc, HW = np.zeros(len(indices), dtype=PAIR_DESC), None
             for row, index in zip(desc, indices):
                 row["h0"], row["w0"] = ds.pair_geometry(index)[:2]
-        cached = all(ds.imgs_rgb[i] is not None for i in indices)
         with torch.cuda.device(self.device), torch.cuda.stream(self._side):
             # Whatever this does to the slot - the table always, the staging buffer when it is reused - comes after the launch that read
             # the slot two batches ago: the consumer stream may be many batches behind the host.
             if slot.consumed is not None:
                 self._side.wait_event(slot.consumed)
-            if cached:
-                sources = [(ds.imgs_rgb[i], ds.imgs_ir[i]) for i in indices]
-                _fill_sources(desc, sources)
-                slot.reserve(0, len(indices), self.device)
-                staged = None
-            else:
-                pairs = list(pool.map(ds.load_pair, indices))
-                offs, total = [], 0
-                for rgb, ir in pairs:
-                    offs.append((total, total + _align16(rgb.nbytes)))
-                    total += _align16(rgb.nbytes) + _align16(ir.nbytes)
-                slot.reserve(total, len(indices), self.device)
-                if ds.cache_images:                      # these bytes stay: the batch's originals live in a buffer of their own
-                    staged = torch.empty(total, dtype=torch.uint8, device=self.device)
-                else:
-                    staged = slot.staged
-                host = slot.pinned.numpy()
-                for (o_rgb, o_ir), (rgb, ir) in zip(offs, pairs):
-                    host[o_rgb:o_rgb + rgb.nbytes] = rgb.reshape(-1)
-                    host[o_ir:o_ir + ir.nbytes] = ir.reshape(-1)
-                staged[:total].copy_(slot.pinned[:total], non_blocking=True)
-                sources = []
-                for (o_rgb, o_ir), (rgb, ir) in zip(offs, pairs):
-                    sources.append((staged[o_rgb:o_rgb + rgb.nbytes].view(rgb.shape), staged[o_ir:o_ir + ir.nbytes].view(ir.shape)))
-                _fill_sources(desc, sources)
-                if ds.cache_images:
-                    for i, (t_rgb, t_ir) in zip(indices, sources):
-                        ds.imgs_rgb[i], ds.imgs_ir[i] = t_rgb, t_ir
+            staged, by_index = self._upload(indices, len(indices), slot, pool)
+            sources = [by_index[i] for i in indices]
+            _fill_sources(desc, sources)
             slot.desc_host[:len(indices)].numpy()[:] = desc.view(np.uint8).reshape(len(indices), -1)
             slot.desc_dev[:len(indices)].copy_(slot.desc_host[:len(indices)], non_blocking=True)
             slot.ready = torch.cuda.Event()
@@ -569,6 +581,386 @@ def create_dataloader_rgb_ir(path1, path2, imgsz, batch_size, stride, opt, hyp=N
                                             image_weights=image_weights,
                                             prefix=prefix)
     return PairLoader(dataset, batch_size, workers=workers, rank=rank, world_size=world_size), dataset
+
+
+# ------------------------------------------------------------------------------ paired RGB + IR dataset, augmented training form
+# The form the reference trains on (train.py:623-626: create_dataloader_rgb_ir(..., augment=True)): per item the mosaic of four pairs
+# or the letterbox, the affine warp, HSV per stream and the flips (utils/datasets.py:1155-1281).  The host draws the random numbers
+# in the reference's order, computes the labels in numpy and writes one table row per output image; everything between the decoded
+# originals and the uint8 [B,6,H,W] batch is ONE launch of cft_augment_batch_u8 per batch (csrc/augment.hip).  It arrives under new
+# names: LoadMultiModalImagesAndLabels(augment=True) and create_dataloader_rgb_ir(quad=True) keep their refusals.
+AUG_TILE = np.dtype([("src_rgb", "<u8"), ("src_ir", "<u8"), ("stride_rgb", "<i8"), ("stride_ir", "<i8"), ("h0", "<i4"), ("w0", "<i4"),
+                     ("h", "<i4"), ("w", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("padw", "<i4"), ("padh", "<i4"),
+                     ("reserved", "<i4", (2,))])
+# one row of the table cft_augment_batch_u8 reads: cft_aug_desc_t of include/cft_hip.h
+AUG_DESC = np.dtype([("ntiles", "<i4"), ("warp", "<i4"), ("canvas_h", "<i4"), ("canvas_w", "<i4"), ("flip", "<i4"), ("reserved", "<i4", (3,)),
+                     ("inv", "<f8", (6,)), ("tile", AUG_TILE, (4,))])
+assert AUG_TILE.itemsize == _lib._consts["CFT_AUG_TILE_BYTES"] and AUG_DESC.itemsize == _lib._consts["CFT_AUG_DESC_BYTES"]
+AUG_FLIPLR, AUG_FLIPUD = _lib._consts["CFT_AUG_FLIPLR"], _lib._consts["CFT_AUG_FLIPUD"]
+AUG_LUT_BYTES = 2 * 3 * 256          # per output image: stream (RGB, IR) x (hue, saturation, value) x 256
+AUG_HYP_KEYS = ('mosaic', 'degrees', 'translate', 'scale', 'shear', 'perspective', 'hsv_h', 'hsv_s', 'hsv_v', 'flipud', 'fliplr')
+
+
+def box_candidates(box1, box2, wh_thr=2, ar_thr=20, area_thr=0.1, eps=1e-16):
+    """Which boxes survive an augmentation, box1 [4, n] before and box2 [4, n] after (reference utils/datasets.py:1917-1922)."""
+    w1, h1 = box1[2] - box1[0], box1[3] - box1[1]
+    w2, h2 = box2[2] - box2[0], box2[3] - box2[1]
+    ar = np.maximum(w2 / (h2 + eps), h2 / (w2 + eps))  # aspect ratio
+    return (w2 > wh_thr) & (h2 > wh_thr) & (w2 * h2 / (w1 * h1 + eps) > area_thr) & (ar < ar_thr)
+
+
+def mosaic_tile_rects(i, xc, yc, w, h, s):
+    """Where tile ``i`` (0 top left, 1 top right, 2 bottom left, 3 bottom right) of resized size (h, w) lands in the 2s x 2s canvas
+    around the centre (xc, yc): ``(x1, y1, x2, y2, padw, padh)``, the arithmetic of load_mosaic_RGB_IR (:1504-1526)."""
+    if i == 0:
+        x1a, y1a, x2a, y2a = max(xc - w, 0), max(yc - h, 0), xc, yc
+        x1b, y1b = w - (x2a - x1a), h - (y2a - y1a)
+    elif i == 1:
+        x1a, y1a, x2a, y2a = xc, max(yc - h, 0), min(xc + w, s * 2), yc
+        x1b, y1b = 0, h - (y2a - y1a)
+    elif i == 2:
+        x1a, y1a, x2a, y2a = max(xc - w, 0), yc, xc, min(s * 2, yc + h)
+        x1b, y1b = w - (x2a - x1a), 0
+    else:
+        x1a, y1a, x2a, y2a = xc, yc, min(xc + w, s * 2), min(s * 2, yc + h)
+        x1b, y1b = 0, 0
+    return x1a, y1a, x2a, y2a, x1a - x1b, y1a - y1b
+
+
+def invert_affine(M):
+    """The inverse of ``M[:2]`` in double by cv2.warpAffine's closed form, ``(a00, a01, a02, a10, a11, a12)``: what the table carries."""
+    m00, m01, m02, m10, m11, m12 = (float(v) for v in np.asarray(M, dtype=np.float64)[:2].reshape(-1))
+    D = m00 * m11 - m01 * m10
+    D = 1.0 / D if D != 0 else 0.0
+    a00, a11 = m11 * D, m00 * D
+    a01, a10 = m01 * -D, m10 * -D
+    return a00, a01, -a00 * m02 - a01 * m12, a10, a11, -a10 * m02 - a11 * m12
+
+
+def hsv_luts(gains):
+    """The three 256-entry tables of augment_hsv (:1379-1382) for ``gains`` = ``uniform(-1, 1, 3) * [h, s, v] + 1``: uint8 [3, 256]."""
+    x = np.arange(0, 256, dtype=np.int16)
+    return np.stack([((x * gains[0]) % 180).astype(np.uint8), np.clip(x * gains[1], 0, 255).astype(np.uint8), np.clip(x * gains[2], 0, 255).astype(np.uint8)])
+
+
+class LoadMultiModalImagesAndLabelsAugmented(LoadMultiModalImagesAndLabels):
+    """The reference's paired dataset with ``augment=True``: mosaic (``not rect``), affine warp, HSV per stream, flips.  Same constructor
+    with ``hyp`` required; the scan, the rect sort and batch shapes, ``labels`` / ``shapes`` / ``n`` / ``indices*`` and ``cache_images`` are
+    the base class's.  An item is not an array here but a plan (``item_plan``): random draws, tile geometry, labels; the pixels of a
+    whole batch come from one cft_augment_batch_u8 launch (``assemble_augmented_batch``, ``AugmentedPairLoader``).
+    Refused: ``image_weights``, ``hyp['perspective'] != 0`` (cv2.warpPerspective), and - where the non-mosaic branch can be reached -
+    a pair whose letterbox would resize a second time."""
+
+    def __init__(self, path_rgb, path_ir, img_size=640, batch_size=16, augment=True, hyp=None, rect=False, image_weights=False,
+                 cache_images=False, single_cls=False, stride=32, pad=0.0, prefix=''):
+        if not augment:
+            raise ValueError("LoadMultiModalImagesAndLabelsAugmented is the augment=True form; LoadMultiModalImagesAndLabels is the other")
+        if hyp is None:
+            raise ValueError("LoadMultiModalImagesAndLabelsAugmented: hyp (the augmentation hyper-parameters) is required")
+        for k in AUG_HYP_KEYS:
+            if k not in hyp:
+                raise ValueError(f"LoadMultiModalImagesAndLabelsAugmented: hyper-parameter '{k}' is missing from hyp")
+        if image_weights:
+            raise NotImplementedError("LoadMultiModalImagesAndLabelsAugmented: image_weights=True (weighted index sampling) is not implemented")
+        if hyp['perspective'] != 0:
+            raise NotImplementedError(f"LoadMultiModalImagesAndLabelsAugmented: hyp['perspective'] = {hyp['perspective']} needs cv2.warpPerspective; "
+                                      "cft_augment_batch_u8 warps with the affine form only (perspective = 0)")
+        super().__init__(path_rgb, path_ir, img_size, batch_size, augment=False, hyp=hyp, rect=rect, image_weights=False,
+                         cache_images=cache_images, single_cls=single_cls, stride=stride, pad=pad, prefix=prefix)
+        self.augment = True
+        self.mosaic = not self.rect
+        self.mosaic_border = [-img_size // 2, -img_size // 2]
+        if self.rect or hyp['mosaic'] < 1:      # the non-mosaic branch can be reached: every pair must be one tile of its letterbox
+            for index, f in enumerate(self.img_files_rgb):
+                h0, w0, h, w, top, left, (H, W), ratio, pad_, new_unpad = self.letterbox_geometry_aug(index)
+                if new_unpad != (w, h):
+                    raise ValueError(f'{prefix}{f} ({w0}x{h0}) is resized to {w}x{h} and its letterbox to {W}x{H} would resize it a second time, to '
+                                     f'{new_unpad[0]}x{new_unpad[1]}: cft_augment_batch_u8 has one resize stage per tile (use mosaic = 1.0 without rect, or another img_size)')
+
+    def _check_sizes(self, prefix=''):
+        """load_image_rgb_ir resizes with INTER_LINEAR in both directions when augmenting: any ratio up to the kernel's size limit."""
+        limit = _lib._consts["CFT_AUG_MAX_SIDE"]
+        for f, (w0, h0) in zip(self.img_files_rgb, self.shapes_rgb.astype(int)):
+            if max(h0, w0, 2 * self.img_size) > limit or min(self.resized_size(h0, w0)) < 1:
+                raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={self.img_size} is outside what cft_augment_batch_u8 takes (sides of 1..{limit})')
+
+    def resized_size(self, h0, w0):
+        """(h, w) of load_image_rgb_ir (:1361-1367)."""
+        r = self.img_size / max(h0, w0)  # ratio
+        return (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
+
+    def letterbox_geometry_aug(self, index):
+        """The non-mosaic branch's geometry (:1202-1209, letterbox(auto=False, scaleup=True)):
+        ``(h0, w0, h, w, top, left, (H, W), ratio, pad, new_unpad)``."""
+        w0, h0 = (int(v) for v in self.shapes_rgb[index])
+        h, w = self.resized_size(h0, w0)
+        shape = self.batch_shapes_rgb[self.batch_rgb[index]] if self.rect else self.img_size  # final letterboxed shape
+        new_unpad, ratio, pad, (top, bottom, left, right) = letterbox_geometry((h, w), shape, auto=False, scaleup=True)
+        return h0, w0, h, w, top, left, (new_unpad[1] + top + bottom, new_unpad[0] + left + right), ratio, pad, new_unpad
+
+    def item_plan(self, index, rng, np_rng):
+        """Everything item ``index`` needs, drawing from ``rng`` (random.Random) and ``np_rng`` (numpy.random.RandomState) in exactly
+        the reference's order: [mosaic decision] [yc, xc, three indices, eight warp draws] two HSV triples, flipud, fliplr.  Returns a dict:
+        ``mosaic``, ``yc``/``xc``, ``indices``, ``tiles`` (dicts index, h0, w0, h, w, x1, y1, x2, y2, padw, padh), ``canvas`` (h, w),
+        ``out`` (H, W), ``M`` (3x3 float64 or None), ``gains`` (two float64 triples), ``flipud``/``fliplr``, ``labels_out`` (float32
+        [nL, 6], column 0 zero), ``shapes``.  Labels follow the reference's operation order: float32 label arrays, float64 M."""
+        hyp, s = self.hyp, self.img_size
+        plan = {"index": index, "yc": None, "xc": None, "M": None}
+        mosaic = self.mosaic and rng.random() < hyp['mosaic']
+        plan["mosaic"] = bool(mosaic)
+        if mosaic:
+            yc, xc = [int(rng.uniform(-x, 2 * s + x)) for x in self.mosaic_border]  # mosaic center x, y
+            indices = [index] + rng.choices(self.indices_rgb, k=3)  # 3 additional image indices
+            tiles, labels4 = [], []
+            for i, k in enumerate(indices):
+                w0, h0 = (int(v) for v in self.shapes_rgb[k])
+                h, w = self.resized_size(h0, w0)
+                x1, y1, x2, y2, padw, padh = mosaic_tile_rects(i, xc, yc, w, h, s)
+                tiles.append({"index": k, "h0": h0, "w0": w0, "h": h, "w": w, "x1": x1, "y1": y1, "x2": x2, "y2": y2, "padw": padw, "padh": padh})
+                labels = self.labels_rgb[k].copy()
+                if labels.size:
+                    labels[:, 1:] = xywhn2xyxy(labels[:, 1:], w, h, padw, padh)  # normalized xywh to pixel xyxy format
+                labels4.append(labels)
+            labels = np.concatenate(labels4, 0)
+            np.clip(labels[:, 1:], 0, 2 * s, out=labels[:, 1:])  # clip when using random_perspective()
+            M, labels = self._random_affine(labels, rng, (2 * s, 2 * s), self.mosaic_border)
+            plan.update(yc=yc, xc=xc, indices=indices, tiles=tiles, canvas=(2 * s, 2 * s), out=(s, s), M=M, shapes=None)
+        else:
+            h0, w0, h, w, top, left, (H, W), ratio, pad, new_unpad = self.letterbox_geometry_aug(index)
+            assert new_unpad == (w, h), f"pair {index}: the letterbox would resize {w}x{h} again"
+            plan.update(indices=[index], canvas=(H, W), out=(H, W), shapes=((h0, w0), ((h / h0, w / w0), pad)),
+                        tiles=[{"index": index, "h0": h0, "w0": w0, "h": h, "w": w, "x1": left, "y1": top, "x2": left + w, "y2": top + h, "padw": left, "padh": top}])
+            labels = self.labels_rgb[index].copy()
+            if labels.size:  # normalized xywh to pixel xyxy format
+                labels[:, 1:] = xywhn2xyxy(labels[:, 1:], ratio[0] * w, ratio[1] * h, padw=pad[0], padh=pad[1])
+        # Augment colorspace: one draw of three per stream, RGB first
+        gains = [np_rng.uniform(-1, 1, 3) * [hyp['hsv_h'], hyp['hsv_s'], hyp['hsv_v']] + 1 for _ in range(2)]
+        H, W = plan["out"]
+        nL = len(labels)  # number of labels
+        if nL:
+            labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])  # convert xyxy to xywh
+            labels[:, [2, 4]] /= H  # normalized height 0-1
+            labels[:, [1, 3]] /= W  # normalized width 0-1
+        flipud = rng.random() < hyp['flipud']
+        if flipud and nL:
+            labels[:, 2] = 1 - labels[:, 2]
+        fliplr = rng.random() < hyp['fliplr']
+        if fliplr and nL:
+            labels[:, 1] = 1 - labels[:, 1]
+        labels_out = torch.zeros((nL, 6))
+        if nL:
+            labels_out[:, 1:] = torch.from_numpy(labels)
+        plan.update(gains=gains, flipud=bool(flipud), fliplr=bool(fliplr), labels_out=labels_out)
+        return plan
+
+    def _random_affine(self, targets, rng, canvas, border):
+        """random_perspective_rgb_ir (:1819-1914) without its image: the eight draws, ``M = T @ S @ R @ P @ C`` and the boxes warped
+        through it, clipped and filtered by ``box_candidates`` (area_thr 0.10).  Returns ``(M, targets)``."""
+        import math
+        hyp = self.hyp
+        height, width = canvas[0] + border[0] * 2, canvas[1] + border[1] * 2
+        C = np.eye(3)
+        C[0, 2] = -canvas[1] / 2  # x translation (pixels)
+        C[1, 2] = -canvas[0] / 2  # y translation (pixels)
+        P = np.eye(3)
+        P[2, 0] = rng.uniform(-hyp['perspective'], hyp['perspective'])  # drawn whatever the value: 0 here
+        P[2, 1] = rng.uniform(-hyp['perspective'], hyp['perspective'])
+        R = np.eye(3)
+        a = rng.uniform(-hyp['degrees'], hyp['degrees'])
+        s = rng.uniform(1 - hyp['scale'], 1 + hyp['scale'])
+        ar = a * np.pi / 180                                             # cv2.getRotationMatrix2D(angle=a, center=(0, 0), scale=s)
+        alpha, beta = np.cos(ar) * s, np.sin(ar) * s
+        R[:2] = [[alpha, beta, 0.0], [-beta, alpha, 0.0]]
+        S = np.eye(3)
+        S[0, 1] = math.tan(rng.uniform(-hyp['shear'], hyp['shear']) * math.pi / 180)  # x shear (deg)
+        S[1, 0] = math.tan(rng.uniform(-hyp['shear'], hyp['shear']) * math.pi / 180)  # y shear (deg)
+        T = np.eye(3)
+        T[0, 2] = rng.uniform(0.5 - hyp['translate'], 0.5 + hyp['translate']) * width  # x translation (pixels)
+        T[1, 2] = rng.uniform(0.5 - hyp['translate'], 0.5 + hyp['translate']) * height  # y translation (pixels)
+        M = T @ S @ R @ P @ C  # order of operations (right to left) is IMPORTANT
+        n = len(targets)
+        if n:
+            xy = np.ones((n * 4, 3))
+            xy[:, :2] = targets[:, [1, 2, 3, 4, 1, 4, 3, 2]].reshape(n * 4, 2)  # x1y1, x2y2, x1y2, x2y1
+            xy = (xy @ M.T)[:, :2].reshape(n, 8)
+            x, y = xy[:, [0, 2, 4, 6]], xy[:, [1, 3, 5, 7]]
+            new = np.concatenate((x.min(1), y.min(1), x.max(1), y.max(1))).reshape(4, n).T
+            new[:, [0, 2]] = new[:, [0, 2]].clip(0, width)
+            new[:, [1, 3]] = new[:, [1, 3]].clip(0, height)
+            i = box_candidates(box1=targets[:, 1:5].T * s, box2=new.T, area_thr=0.10)
+            targets = targets[i]
+            targets[:, 1:5] = new[i]
+        return M, targets
+
+    def plan_targets(self, plans):
+        """``(targets [nt, 6] float32 CPU, paths, shapes)`` of one planned batch: the reference's ``collate_fn`` (:1284-1288)."""
+        label = [p["labels_out"].clone() for p in plans]
+        for i, l in enumerate(label):
+            l[:, 0] = i  # add target image index for build_targets()
+        return torch.cat(label, 0), tuple(self.img_files_rgb[p["index"]] for p in plans), tuple(p["shapes"] for p in plans)
+
+
+def build_augment_descriptors(plans):
+    """The table and the look-up tables of cft_augment_batch_u8 for one planned batch, source pointers and strides left zero:
+    ``(AUG_DESC array [B], uint8 [B, 2, 3, 256], (H, W))``."""
+    table = np.zeros(len(plans), dtype=AUG_DESC)
+    luts = np.empty((len(plans), 2, 3, 256), dtype=np.uint8)
+    HW = None
+    for row, lut, p in zip(table, luts, plans):
+        if HW is not None and tuple(p["out"]) != HW:
+            raise AssertionError(f"item {p['index']}: output {tuple(p['out'])} differs from its batch's {HW}")
+        HW = tuple(p["out"])
+        row["ntiles"], row["warp"] = len(p["tiles"]), int(p["M"] is not None)
+        row["canvas_h"], row["canvas_w"] = p["canvas"]
+        row["flip"] = (AUG_FLIPLR if p["fliplr"] else 0) | (AUG_FLIPUD if p["flipud"] else 0)
+        if p["M"] is not None:
+            row["inv"] = invert_affine(p["M"])
+        for tile, t in zip(row["tile"], p["tiles"]):
+            for k in ("h0", "w0", "h", "w", "x1", "y1", "x2", "y2", "padw", "padh"):
+                tile[k] = t[k]
+        lut[0], lut[1] = hsv_luts(p["gains"][0]), hsv_luts(p["gains"][1])
+    return table, luts, HW
+
+
+def _fill_aug_sources(table, plans, by_index):
+    """Source pointers and strides of every tile from ``by_index``: {pair index: (rgb, ir) HWC RGB uint8 CUDA tensors}."""
+    for row, p in zip(table, plans):
+        for tile, t in zip(row["tile"], p["tiles"]):
+            rgb, ir = by_index[t["index"]]
+            for x in (rgb, ir):
+                if x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3 or x.stride(2) != 1 or x.stride(1) != 3 or not x.is_cuda:
+                    raise ValueError("pair sources must be HWC uint8 CUDA tensors with contiguous pixels")
+                if tuple(x.shape[:2]) != (t["h0"], t["w0"]):
+                    raise ValueError(f"pair source is {tuple(x.shape[:2])}, the table says {(t['h0'], t['w0'])}")
+            tile["src_rgb"], tile["src_ir"], tile["stride_rgb"], tile["stride_ir"] = rgb.data_ptr(), ir.data_ptr(), rgb.stride(0), ir.stride(0)
+
+
+def augment_batch(table, luts, out):
+    """Launch cft_augment_batch_u8: ``table`` a filled AUG_DESC array and ``luts`` uint8 [B, 2, 3, 256] (host), ``out`` the uint8 CUDA
+    [B, 6, H, W] batch to write.  The device copies are made on the current stream from pinned memory."""
+    from ..ops import augment_batch_u8
+    host = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(len(table), -1)).pin_memory()
+    luts_host = torch.from_numpy(np.ascontiguousarray(luts)).pin_memory()
+    augment_batch_u8(host.to(out.device, non_blocking=True), host, luts_host.to(out.device, non_blocking=True), out)
+    return out
+
+
+def assemble_augmented_batch(dataset, indices, device, rng, np_rng, sources=None, return_plans=False):
+    """One augmented batch assembled directly: plan every item (drawing from ``rng`` / ``np_rng`` item by item, as one pass over the
+    reference's dataset does), decode each distinct pair once (or take ``sources``: {pair index: (rgb, ir) HWC RGB uint8 CUDA tensors}),
+    upload, one launch.  Returns the uint8 [B, 6, H, W] CUDA tensor (and the plans).  ``AugmentedPairLoader`` does the same with
+    staging buffers and prefetch."""
+    plans = [dataset.item_plan(i, rng, np_rng) for i in indices]
+    if sources is None:
+        sources = {k: tuple(torch.from_numpy(a).to(device) for a in dataset.load_pair(k)) for k in sorted({t["index"] for p in plans for t in p["tiles"]})}
+    table, luts, (H, W) = build_augment_descriptors(plans)
+    _fill_aug_sources(table, plans, sources)
+    out = augment_batch(table, luts, torch.empty((len(plans), 6, H, W), dtype=torch.uint8, device=device))
+    return (out, plans) if return_plans else out
+
+
+def batch_seed(seed, epoch, batch):
+    """The 64-bit seed of one batch's generators, an explicit integer mix of (seed, epoch, batch index): the three are combined with
+    three odd 64-bit constants and passed through the splitmix64 finaliser, all modulo 2^64.  It depends on nothing else - not on
+    which batches were planned before, on prefetch timing or on the rank that assembles the batch."""
+    m = (1 << 64) - 1
+    x = (0x9E3779B97F4A7C15 * (int(seed) + 1) + 0xBF58476D1CE4E5B9 * (int(epoch) + 1) + 0x94D049BB133111EB * (int(batch) + 1)) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
+
+
+def batch_generators(seed, epoch, batch):
+    """``(random.Random, numpy.random.RandomState)`` of one batch: the first seeded with ``batch_seed``, the second with its two halves."""
+    import random
+    x = batch_seed(seed, epoch, batch)
+    return random.Random(x), np.random.RandomState([x & 0xFFFFFFFF, x >> 32])
+
+
+class AugmentedPairLoader(PairLoader):
+    """The iterable ``create_train_dataloader_rgb_ir`` returns: yields ``(img6 uint8 cuda [B, 6, H, W], targets float32 CPU [nt, 6],
+    paths, shapes)`` per batch in dataset order (the reference's loader does not shuffle).  Decode pool, the two staging slots and the
+    side stream are ``PairLoader``'s; a batch's up-to-4B distinct pairs are decoded once each, and with ``cache_images`` only the
+    table and the look-up tables are uploaded once the originals are on the device.  The next batch is planned on the stager thread,
+    so the global ``random`` / ``np.random`` are never touched: batch ``b`` of epoch ``e`` draws from ``batch_generators(seed, e, b)``.
+    ``set_epoch(e)`` sets the epoch of the next pass; otherwise every ``__iter__`` advances it."""
+
+    def __init__(self, dataset, batch_size, workers=8, rank=-1, world_size=1, device=None, seed=0):
+        super().__init__(dataset, batch_size, workers=workers, rank=rank, world_size=world_size, device=device)
+        self.seed = int(seed)
+        self.epoch = 0
+        self._slots = (_Slot(AUG_DESC.itemsize + AUG_LUT_BYTES), _Slot(AUG_DESC.itemsize + AUG_LUT_BYTES))
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def plan_batch(self, b, epoch):
+        """The plans of batch ``b`` of epoch ``epoch``: a function of (seed, epoch, b) and the dataset alone."""
+        rng, np_rng = batch_generators(self.seed, epoch, b)
+        return [self.dataset.item_plan(i, rng, np_rng) for i in self.batch_indices(b)]
+
+    def _stage(self, b, slot, pool, epoch):
+        """Plan, decode and upload batch ``b`` (side stream); returns what ``_assemble`` needs."""
+        plans = self.plan_batch(b, epoch)
+        n = len(plans)
+        table, luts, HW = build_augment_descriptors(plans)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            if slot.consumed is not None:                # after the launch that read this slot two batches ago
+                self._side.wait_event(slot.consumed)
+            staged, by_index = self._upload(sorted({t["index"] for p in plans for t in p["tiles"]}), n, slot, pool)
+            _fill_aug_sources(table, plans, by_index)
+            host = slot.desc_host[:n].view(-1).numpy()   # the table, then the look-up tables, in one upload
+            host[:n * AUG_DESC.itemsize] = table.view(np.uint8).reshape(-1)
+            host[n * AUG_DESC.itemsize:] = luts.reshape(-1)
+            slot.desc_dev[:n].copy_(slot.desc_host[:n], non_blocking=True)
+            slot.ready = torch.cuda.Event()
+            slot.ready.record(self._side)
+        return plans, HW, staged, by_index
+
+    def _assemble(self, slot, plans, HW, staged, by_index):
+        from ..ops import augment_batch_u8
+        n, nb = len(plans), len(plans) * AUG_DESC.itemsize
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(slot.ready)
+        out = torch.empty((n, 6, HW[0], HW[1]), dtype=torch.uint8, device=self.device)
+        dev, host = slot.desc_dev[:n].view(-1), slot.desc_host[:n].view(-1)
+        augment_batch_u8(dev[:nb].view(n, -1), host[:nb].view(n, -1), dev[nb:].view(n, 2, 3, 256), out)
+        slot.consumed = torch.cuda.Event()
+        slot.consumed.record(cur)
+        slot.desc_dev.record_stream(cur)                 # allocated on the side stream, read on this one
+        if staged is not None:
+            staged.record_stream(cur)
+        return out
+
+    def __iter__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        batches = list(self.batch_range)
+        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
+            nxt = stager.submit(self._stage, batches[0], self._slots[0], pool, epoch) if batches else None
+            for k, b in enumerate(batches):
+                staged = nxt.result()
+                slot = self._slots[k % 2]
+                # the next batch is planned, decoded and uploaded while this one is assembled and used
+                nxt = stager.submit(self._stage, batches[k + 1], self._slots[(k + 1) % 2], pool, epoch) if k + 1 < len(batches) else None
+                img = self._assemble(slot, *staged)
+                targets, paths, shapes = self.dataset.plan_targets(staged[0])
+                yield img, targets, paths, shapes
+
+
+def create_train_dataloader_rgb_ir(path1, path2, imgsz, batch_size, stride, opt, hyp, cache=False, rect=False, rank=-1, world_size=1,
+                                   workers=8, seed=0, prefix='', pad=0.0, image_weights=False, quad=False):
+    """What train.py:623-626 builds with ``create_dataloader_rgb_ir(..., augment=True)``: returns ``(loader, dataset)`` with the
+    loader an ``AugmentedPairLoader``.  ``opt`` is read for ``single_cls`` only; with ``rank >= 0`` the loader yields that rank's
+    contiguous range of batches (``distributed.shard_bounds``)."""
+    if quad:
+        raise NotImplementedError("create_train_dataloader_rgb_ir: quad=True (collate_fn4) is not implemented")
+    dataset = LoadMultiModalImagesAndLabelsAugmented(path1, path2, imgsz, batch_size, augment=True, hyp=hyp, rect=rect, cache_images=cache,
+                                                     single_cls=opt.single_cls, stride=int(stride), pad=pad, image_weights=image_weights,
+                                                     prefix=prefix)
+    return AugmentedPairLoader(dataset, batch_size, workers=workers, rank=rank, world_size=world_size, seed=seed), dataset
 
 
 # ------------------------------------------------------------------------------ inference loaders (detect_twostream.py)
