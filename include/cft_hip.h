@@ -290,6 +290,84 @@ typedef struct {
 } cft_aug_desc_t;
 int cft_augment_batch_u8(const void* desc_dev, const void* desc_host, const unsigned char* luts, int B, unsigned char* dst, int dst_h, int dst_w, void* stream);
 
+/*
+ * Baseline JPEG decoding in two halves (no reference counterpart: the reference hands every file to cv2.imread).  The yardstick is
+ * PIL's decode of the same bytes (libjpeg-turbo, JDCT_ISLOW, fancy upsampling), np.array(Image.open(f).convert('RGB')), byte for byte.
+ *
+ * HOST half - plain C++, no HIP call, no GPU needed, re-entrant: no shared mutable state, not even cft_last_error's text; results
+ * travel in the return code and in caller memory, so many threads may call it at once.  Neither function reads past nbytes or writes
+ * past the sizes cft_jpeg_info reported, whatever the bytes are.
+ *   cft_jpeg_info(bytes, nbytes, info): parses the markers up to SOS and fills a cft_jpeg_info_t (host, CFT_JPEG_INFO_BYTES).
+ *   cft_jpeg_entropy(bytes, nbytes, coef, qtab, info): Huffman-decodes the single interleaved scan into QUANTISED int16 coefficients:
+ *     coef holds info->ncoef values, component after component (component c starts at 64 * sum_{k<c} bw[k] * bh[k]), blocks in
+ *     raster order of the component's bw x bh grid, 64 values per block in natural (de-zigzagged) order; every value is written.
+ *     qtab: uint16 [3][64], the quantisation table of each component in natural order (rows of absent components are zero).
+ *     info: what cft_jpeg_info returned for the same bytes (checked against the file again: CFT_EINVAL when it differs).
+ *   Return: CFT_OK, CFT_EINVAL (null pointer, nbytes < 1, info of another file) or CFT_JPEG_UNSUPPORTED: the file is outside the subset
+ *   and the caller decodes it with PIL.  Supported: SOF0, 8-bit samples, 8-bit quantisation tables, one scan holding every component,
+ *   sides 1..CFT_JPEG_MAX_SIDE; 1 component sampled 1x1, or 3 components with luma 1x1, 2x1 or 2x2 (h x v) and chroma 1x1; JFIF or no
+ *   colour marker, or an Adobe marker with transform 1.  Unsupported: anything else - not a JPEG, an Adobe marker with another transform,
+ *   component ids 'R' 'G' 'B' without a JFIF marker, 4 components, progressive / arithmetic / 12-bit coding, a DNL marker, no EOI after
+ *   the scan, a wrong or missing restart marker, truncated or corrupt entropy data, any coefficient with |coef| * q > 32767 - and a
+ *   chroma component halved horizontally whose downsampled width is <= 2, where libjpeg replicates pixels instead of filtering (kept
+ *   when that width is 1 and the component is one row high or not halved vertically: both methods then give the same bytes).
+ *
+ * DEVICE half - cft_jpeg_decode_u8 decodes n images in one call: two launches on the stream, no atomics, every output byte written
+ * once.  table_dev (device) / table_host (host, the same bytes, what the guards read) hold one cft_jpeg_desc_t row per image.  Every
+ * row is checked before the launch and nothing is launched on CFT_EINVAL: null or misaligned pointers (coef 2, qtab 2, plane_off and
+ * the workspace 16), sides 1..CFT_JPEG_MAX_SIDE, sampling in the subset, bw / bh equal to the padded block grid of that geometry,
+ * dst_stride >= 3 * width, [plane_off, plane_off + 64 * blocks) inside workspace_bytes and at or after the end of the previous
+ * row's range (the ranges ascend, so no two overlap).
+ * 1 <= n <= 65535.  The kernels clamp their own indices as well.
+ *   1. jpeg_idct_kernel, 8 lanes per 8x8 block: dequantise (coef * q, int32), then libjpeg's jpeg_idct_islow (CONST_BITS 13,
+ *      PASS1_BITS 2; FIX constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172; the published butterfly):
+ *      columns first, descaled by 11, the transpose through LDS, then rows, descaled by 18, DESCALE(x, n) = (x + (1 << (n-1))) >> n,
+ *      + 128, saturated to 0..255.  A lane stores the 8 bytes of its row as one 8-byte word into the component's plane in the
+ *      workspace: component c is a (8 bh[c]) x (8 bw[c]) byte plane at plane_off + 64 * sum_{k<c} bw[k] * bh[k], row stride 8 bw[c].
+ *   2. jpeg_colour_kernel, one thread per 4 consecutive pixels of an output row.  Chroma is upsampled over the component's
+ *      DOWNSAMPLED size cw x ch = ceil(width * h / hmax) x ceil(height * v / vmax); the padding samples of the IDCT are never read:
+ *      every neighbour index is clamped into [0, cw) x [0, ch), which is what the edge rules below amount to.
+ *        h2v1: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2, out[0] = in[0], out[2 cw - 1] = in[cw-1].
+ *        h2v2: the neighbouring row is the one above for an even output row, the one below for an odd one (at the top and bottom the
+ *              component's own first / last row); s[i] = 3 in_row[i] + in_neighbour[i]; out[2i] = (3 s[i] + s[i-1] + 8) >> 4,
+ *              out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4; the first output is (4 s[0] + 8) >> 4, the last (4 s[cw-1] + 7) >> 4.
+ *      Colour, cb and cr centred at 128, arithmetic shifts, results clamped to 0..255:
+ *        R = Y + ((91881 cr + 32768) >> 16),  B = Y + ((116130 cb + 32768) >> 16),  G = Y + ((-22554 cb - 46802 cr + 32768) >> 16).
+ *      One component: R = G = B = Y (what convert('RGB') does to mode L).  dst is HWC RGB uint8, pixel (y, x) at dst + y * dst_stride + 3 x.
+ */
+#define CFT_JPEG_UNSUPPORTED 1
+#define CFT_JPEG_MAX_SIDE 16384
+#define CFT_JPEG_INFO_BYTES 128
+#define CFT_JPEG_DESC_BYTES 96
+#define CFT_JPEG_QTAB_BYTES 384
+typedef struct {
+  int width, height;
+  int ncomp;                      /* 1 or 3 */
+  int hmax, vmax;                 /* the luma sampling factors */
+  int mcus_x, mcus_y;
+  int restart_interval;           /* MCUs between restart markers, 0 = none */
+  int hs[3], vs[3];               /* per component: sampling factors, */
+  int bw[3], bh[3];               /*   block grid padded to whole MCUs, */
+  int cw[3], ch[3];               /*   downsampled size in samples */
+  int reserved[2];
+  long ncoef;                     /* int16 coefficients of the file: 64 * sum bw * bh */
+  long plane_bytes;               /* bytes of plane workspace: 64 * sum bw * bh */
+} cft_jpeg_info_t;
+typedef struct {
+  const short* coef;              /* device: what cft_jpeg_entropy wrote */
+  const unsigned short* qtab;     /* device: uint16 [3][64] */
+  unsigned char* dst;             /* device: HWC RGB uint8 */
+  long dst_stride;                /* bytes per row of dst, >= 3 * width */
+  long plane_off;                 /* where this image's planes start in the workspace, a multiple of 16 */
+  int width, height;
+  int ncomp, hmax, vmax;
+  int bw[3], bh[3];
+  int reserved[3];
+} cft_jpeg_desc_t;
+int cft_jpeg_info(const unsigned char* bytes, long nbytes, cft_jpeg_info_t* info);
+int cft_jpeg_entropy(const unsigned char* bytes, long nbytes, short* coef, unsigned short* qtab, const cft_jpeg_info_t* info);
+int cft_jpeg_decode_u8(const void* table_dev, const void* table_host, int n, void* workspace, long workspace_bytes, void* stream);
+
 /* Elementwise out = a + b over M pixels x C channels (Add / Add2, models/common.py:228-243). */
 int cft_add(const void* a, int lda, int aoff, const void* b, int ldb, int boff,
             void* out, int ldo, int ooff, long M, int C, int dtype, void* stream);

@@ -188,6 +188,30 @@ def decode_image(path):
         return np.array(im.convert('RGB'))
 
 
+def use_device_jpeg(dataset_or_loader, enabled=True):
+    """Switch the loaders of a paired dataset (or of the loader given) to decoding baseline JPEG files on the GPU: the Huffman half on
+    the decode pool (cft_jpeg_entropy), dequantisation, IDCT, chroma upsampling and colour conversion in one cft_jpeg_decode_u8 call per
+    batch, byte for byte what PIL decodes.  Files that are not JPEG or not in the supported subset (include/cft_hip.h) go through PIL as
+    before, judged per file.  ``enabled=False`` switches back.  Returns its argument."""
+    ds = getattr(dataset_or_loader, "dataset", dataset_or_loader)
+    if not hasattr(ds, "decode"):
+        raise TypeError(f"use_device_jpeg: {type(dataset_or_loader).__name__} is neither a paired dataset nor its loader")
+    ds.decode = 'device' if enabled else 'pil'
+    return dataset_or_loader
+
+
+def _probe_jpeg(path):
+    """``(bytes, info)`` of a file the device decoder takes, ``(None, None)`` for every other file (it is then read by PIL)."""
+    from .jpeg import jpeg_info
+    with open(path, 'rb') as f:
+        if f.read(2) != b'\xff\xd8':
+            return None, None
+        f.seek(0)
+        blob = f.read()
+    info = jpeg_info(blob)
+    return (blob, info) if info is not None else (None, None)
+
+
 class LoadMultiModalImagesAndLabels:  # for testing
     """The reference's paired RGB + IR dataset (utils/datasets.py:820-1288), same constructor, in its non-augmented form:
     ``augment=True`` (mosaic, HSV, flips, perspective) raises NotImplementedError.  Differences that are deliberate:
@@ -219,6 +243,8 @@ class LoadMultiModalImagesAndLabels:  # for testing
         self.path_ir = path_ir
         self.pad = pad
         self.cache_images = bool(cache_images)
+        self.decode = 'pil'      # 'device': the loaders decode baseline JPEG files on the GPU (use_device_jpeg), everything else stays with PIL
+        self.jpeg_infos = {}     # decode = 'device': path -> cft_jpeg_info of the file, None for a file that PIL has to decode
 
         try:
             files_rgb, files_ir = _list_images(path_rgb, prefix), _list_images(path_ir, prefix)
@@ -432,6 +458,7 @@ class _Slot:
     def __init__(self, row_bytes=PAIR_DESC.itemsize):
         self.row_bytes = row_bytes                 # bytes of table per batch row
         self.pinned = self.staged = self.desc_host = self.desc_dev = None
+        self.jpinned = self.jstaged = None      # decode = 'device': table + coefficients + tables (pinned), the same + planes (device)
         self.ready = self.consumed = None       # upload finished (side stream) / batch assembled (consumer stream)
 
     def reserve(self, nbytes, nrows, device):
@@ -444,13 +471,23 @@ class _Slot:
             self.desc_host = torch.empty((nrows, self.row_bytes), dtype=torch.uint8).pin_memory()
             self.desc_dev = torch.empty((nrows, self.row_bytes), dtype=torch.uint8, device=device)
 
+    def reserve_jpeg(self, upload_bytes, device_bytes, device):
+        """After ``reserve`` (which has waited for the previous upload): room for ``upload_bytes`` of pinned JPEG staging and
+        ``device_bytes`` >= that on the device (the upload, then the plane workspace)."""
+        if self.jpinned is None or self.jpinned.numel() < upload_bytes:
+            self.jpinned = torch.empty(upload_bytes, dtype=torch.uint8).pin_memory()
+        if self.jstaged is None or self.jstaged.numel() < device_bytes:
+            self.jstaged = torch.empty(device_bytes, dtype=torch.uint8, device=device)
+
 
 class PairLoader:
     """The iterable ``create_dataloader_rgb_ir`` returns: yields ``(img6 uint8 cuda [B, 6, H, W], targets float32 CPU [nt, 6], paths,
     shapes)`` per batch, in dataset order.  While a batch is in use the next one is decoded (PIL, a pool of ``workers`` threads),
     staged into a reused pinned buffer and uploaded on a side stream; an event recorded there is what the consumer stream waits on
     before the batch's single cft_pair_batch_u8 launch, and an event recorded after that launch is what the side stream waits on
-    before it overwrites the slot's table and staging buffer two batches later (cached batches included: they reuse the table)."""
+    before it overwrites the slot's table and staging buffer two batches later (cached batches included: they reuse the table).
+    With ``dataset.decode == 'device'`` (``use_device_jpeg``) the pool only Huffman-decodes the JPEG files and their pixels are made on
+    the side stream by one cft_jpeg_decode_u8 call per batch (``_upload_device``)."""
 
     def __init__(self, dataset, batch_size, workers=8, rank=-1, world_size=1, device=None):
         self.dataset = dataset
@@ -482,6 +519,8 @@ class PairLoader:
         if not missing:
             slot.reserve(0, nrows, self.device)
             return None, by_index
+        if ds.decode == 'device':
+            return self._upload_device(missing, by_index, nrows, slot, pool)
         pairs = list(pool.map(ds.load_pair, missing))
         offs, total = [], 0
         for rgb, ir in pairs:
@@ -499,6 +538,85 @@ class PairLoader:
         staged[:total].copy_(slot.pinned[:total], non_blocking=True)
         for i, (o_rgb, o_ir), (rgb, ir) in zip(missing, offs, pairs):
             by_index[i] = (staged[o_rgb:o_rgb + rgb.nbytes].view(rgb.shape), staged[o_ir:o_ir + ir.nbytes].view(ir.shape))
+            if ds.cache_images:
+                ds.imgs_rgb[i], ds.imgs_ir[i] = by_index[i]
+        return staged, by_index
+
+    def _upload_device(self, missing, by_index, nrows, slot, pool):
+        """``_upload`` with ``dataset.decode == 'device'``: every file of the pairs ``missing`` that the device decoder takes is read and
+        Huffman-decoded on the pool straight into the slot's pinned JPEG staging (table rows, then per file coefficients and quantisation
+        tables), uploaded in one copy and turned into its HWC RGB original by one cft_jpeg_decode_u8 call on the current (side) stream;
+        the originals land in ``staged`` where ``_upload`` would have copied them and never exist on the host.  Any other file - not a
+        JPEG, outside the subset, refused by the entropy decoder - is decoded by PIL into the pinned image staging as before and uploaded
+        with the rest in a second copy.  Same return value as ``_upload``."""
+        from .jpeg import JPEG_DESC, QTAB_BYTES, fill_desc, jpeg_decode_u8, jpeg_entropy
+        ds = self.dataset
+        files = [(i, (ds.img_files_rgb, ds.img_files_ir)[s][i]) for i in missing for s in (0, 1)]
+        probed = []                                                  # (bytes or None, info or None) per file; the header is parsed once per file
+        for _, f in files:
+            if f in ds.jpeg_infos:
+                probed.append((None, ds.jpeg_infos[f]))
+            else:
+                probed.append(_probe_jpeg(f))
+                ds.jpeg_infos[f] = probed[-1][1]
+        offs, total = [], 0                                          # the originals in staged, as _upload lays them out
+        joffs, jtotal, planes = [], _align16(len(files) * JPEG_DESC.itemsize), 0
+        for (i, f), (blob, info) in zip(files, probed):
+            w0, h0 = (int(v) for v in ds.shapes_rgb[i])
+            if info is not None and (int(info["width"]), int(info["height"])) != (w0, h0):
+                raise ValueError(f'{f}: decodes to {int(info["width"])}x{int(info["height"])}, scanned as {w0}x{h0}')
+            offs.append(total)
+            total += _align16(h0 * w0 * 3)
+            joffs.append(jtotal)
+            if info is not None:
+                jtotal += _align16(2 * int(info["ncoef"])) + QTAB_BYTES
+                planes += _align16(int(info["plane_bytes"]))
+        slot.reserve(total, nrows, self.device)
+        slot.reserve_jpeg(jtotal, jtotal + planes, self.device)
+        staged = torch.empty(total, dtype=torch.uint8, device=self.device) if ds.cache_images else slot.staged
+        host, jhost = slot.pinned.numpy(), slot.jpinned.numpy()
+
+        def work(k):
+            """True: file k's coefficients are in the JPEG staging; False: its PIL decode is in the image staging."""
+            (i, f), (blob, info) = files[k], probed[k]
+            if info is not None:
+                if blob is None:
+                    with open(f, 'rb') as fh:
+                        blob = fh.read()
+                nc = 2 * int(info["ncoef"])
+                q0 = joffs[k] + _align16(nc)
+                if jpeg_entropy(blob, info, jhost[joffs[k]:joffs[k] + nc].view(np.int16), jhost[q0:q0 + QTAB_BYTES].view(np.uint16)):
+                    return True
+            im = decode_image(f)
+            w0, h0 = (int(v) for v in ds.shapes_rgb[i])
+            if im.shape != (h0, w0, 3):
+                raise ValueError(f'{f}: decoded to {im.shape[1]}x{im.shape[0]}, scanned as {w0}x{h0}')
+            host[offs[k]:offs[k] + im.nbytes] = im.reshape(-1)
+            return False
+
+        on_device = list(pool.map(work, range(len(files))))
+        live = [k for k, d in enumerate(on_device) if d]
+        by_pil = [k for k, d in enumerate(on_device) if not d]
+        if by_pil:
+            lo = offs[by_pil[0]]
+            w0, h0 = (int(v) for v in ds.shapes_rgb[files[by_pil[-1]][0]])
+            hi = offs[by_pil[-1]] + h0 * w0 * 3
+            staged[lo:hi].copy_(slot.pinned[lo:hi], non_blocking=True)
+        if live:
+            table = np.zeros(len(live), dtype=JPEG_DESC)
+            plane_off = 0
+            for row, k in zip(table, live):
+                info = probed[k][1]
+                coef = slot.jstaged.data_ptr() + joffs[k]
+                fill_desc(row, info, coef, coef + _align16(2 * int(info["ncoef"])), staged.data_ptr() + offs[k], 3 * int(info["width"]), plane_off)
+                plane_off += _align16(int(info["plane_bytes"]))
+            nb = len(live) * JPEG_DESC.itemsize
+            jhost[:nb] = table.view(np.uint8).reshape(-1)
+            slot.jstaged[:jtotal].copy_(slot.jpinned[:jtotal], non_blocking=True)
+            jpeg_decode_u8(slot.jstaged[:nb], slot.jpinned[:nb], len(live), slot.jstaged[jtotal:jtotal + planes])
+        for n, i in enumerate(missing):
+            w0, h0 = (int(v) for v in ds.shapes_rgb[i])
+            by_index[i] = tuple(staged[offs[2 * n + s]:offs[2 * n + s] + h0 * w0 * 3].view(h0, w0, 3) for s in (0, 1))
             if ds.cache_images:
                 ds.imgs_rgb[i], ds.imgs_ir[i] = by_index[i]
         return staged, by_index
