@@ -12,7 +12,22 @@ struct Bneck128Params {
   unsigned char* y;
   int ldx, xoff, ldy, yoff, kpad1, kpad2;
   int H, W, tiles_x, tiles_y, ntiles, shortcut;
+  uint32_t m_tiles, m_tiles_x;   // bneck_magic(tiles_x * tiles_y), bneck_magic(tiles_x): the kernels divide tile ids without a divider
 };
+
+// floor(2^32 / d) for the mul-hi division below (d >= 1; d = 1 saturates)
+static inline uint32_t bneck_magic(int d) { return d <= 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / (unsigned)d); }
+// n / d and the remainder for 0 <= n < 2^31 with m = bneck_magic(d): the mul-hi estimate is the quotient or one less
+// (n (2^32 / d - m) < 2^31), so one correction step makes it exact.  Wave-uniform operands stay on the scalar unit.
+__device__ __forceinline__ int bneck_divmod(int n, int d, uint32_t m, int& rem) {
+  int q = (int)__umulhi((uint32_t)n, m);
+  int r = n - q * d;
+  if (r >= d) { ++q; r -= d; }
+  rem = r;
+  return q;
+}
 
 // bottleneck_asm.hip: the 128-channel Bottleneck on 16 x 16-pixel tiles with the hand-scheduled 3x3 loop (dtype CFT_BF16 / CFT_F16)
 int bneck128_asm_launch(const Bneck128Params& p, int dtype, hipStream_t stream);
+// probes/bottleneck_r6.hip: the round-6 form of the two product kernels (c = 64 / 128), for A/B timing in the probe build
+int bneck_r6_launch(const Bneck128Params& p, int c, int dtype, hipStream_t stream);

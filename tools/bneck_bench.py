@@ -1,6 +1,7 @@
 """Time cft_bottleneck against the two cft_conv2d launches it replaces, and (probe build only: tools/build_probes.sh) its ablation probes.
-    python tools/bneck_bench.py [C] [variants]      C = 64 (160x160 stage) or 128 (80x80 stage), batch 64
-variant 0 = the shipped kernel.  Probe build, 64 channels: 9601 / 9602 / 9604 / 9608 = without W1-stage MFMAs / 3x3 MFMAs / epilogue /
+    python tools/bneck_bench.py [C] [variants] [iters]      C = 64 (160x160 stage) or 128 (80x80 stage), batch 64; iters launches per timing (20)
+variant 0 = the shipped kernel; a variant may be named several times (A/B/A/B: "95,0,95,0,95,0"), every pass is kept.  Probe build:
+95 = the kernels before the instruction diet (profiles/bottleneck_valu.md); 64 channels: 9601 / 9602 / 9604 / 9608 = without W1-stage MFMAs / 3x3 MFMAs / epilogue /
 weight DMA; 128 channels: 9201 / 9202 / 9204 / 9208 = the same, 9456 = no x requests, 9712 = no SiLU."""
 import json
 import os
@@ -46,6 +47,7 @@ def main():
     out = ops.new_nhwc(B, H, W, C, torch.bfloat16, dev)
     t = ops.new_nhwc(B, H, W, C, torch.bfloat16, dev)
     only = len(sys.argv) > 2 and [int(v) for v in sys.argv[2].split(",")]
+    iters = int(sys.argv[3]) if len(sys.argv) > 3 else 20
     flops = 2.0 * B * H * W * C * C * 10
     res = {"C": C, "gflop": flops / 1e9}
     if not only:
@@ -55,8 +57,8 @@ def main():
     probes = "probes" in os.path.basename(getattr(_lib, "LIB_PATH", ""))
     for v in (only or ((0, 9601, 9602, 9604, 9608) if C == 64 else ((0, 98, 0, 98, 9301, 9302, 9304, 9308, 9303, 9306, 9305) if probes else (0,)))):
         lib.cft_set_conv_variant(v)
-        us = timeit(lambda: ops.bottleneck(x, pk1, pk2, True, out=out))
-        res[f"fused_v{v}_us"] = round(us, 1)
+        us = timeit(lambda: ops.bottleneck(x, pk1, pk2, True, out=out), iters=iters)
+        res.setdefault(f"fused_v{v}_us", []).append(round(us, 1))
         print(f"fused variant {v}: {us:.1f} us  ({flops / us / 1e6:.0f} TFLOP/s)")
     lib.cft_set_conv_variant(0)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
