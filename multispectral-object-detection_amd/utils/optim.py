@@ -13,7 +13,9 @@ uploaded only when a pointer, a size or the set of parameters that have a gradie
 weight_decay / nesterov travel in the kernel arguments, so the warm-up's per-iteration edits of ``param_groups`` cost nothing.
 
 ``Adam`` / ``AdamW`` (the reference's ``--adam``, ``build_adam_optimizer``) work the same way through ``cft_adam_step``; their per-
-parameter step counts stay on the device.
+parameter step counts stay on the device.  ``step()`` itself is written once, in ``_TableOptimizer``: an optimiser adds only its
+hyper-parameter row, its state tensors and its entry point, and ``DeviceTable.call`` is the one place that calls the library
+(``ModelEMA`` uses it too).
 
 The kernel writes the parameters through raw pointers; ``step()`` then bumps their version counters, which is what ``Model`` reads to
 decide that its packed weights and captured graphs are stale.
@@ -83,6 +85,13 @@ class DeviceTable:
         self.uploads += 1
         return True
 
+    def call(self, entry, max_blocks, *args):
+        """The library call ``entry`` on the table as it is: the six table arguments, ``args``, the current stream of its device."""
+        with torch.cuda.device(self.device):
+            st = getattr(_lib.load(), entry)(self.dev.data_ptr(), self.host.data_ptr(), self.nseg, self.nwork, self.chunk, max_blocks, *args,
+                                             torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(st, entry)
+
 
 def _check_tensor(t, like, what, name):
     if t.dtype != torch.float32:
@@ -101,6 +110,17 @@ def _check_tensor(t, like, what, name):
         raise ValueError(f"{what}: {name} must have the memory layout of its partner (strides {tuple(t.stride())} / {tuple(like.stride())})")
 
 
+def _one_device(device, t, errors):
+    """The one device of a table, for a tensor ``t`` that is not on ``device``: the first tensor fixes it (``device`` is None) and
+    must be on a GPU, any other is an error.  ``errors``: the texts for a first tensor elsewhere (``{0}``: where) and for a second
+    device (``{0}`` and ``{1}``)."""
+    if device is not None:
+        raise ValueError(errors[1].format(device, t.device))
+    if t.device.type != "cuda":
+        raise ValueError(errors[0].format(t.device))
+    return t.device
+
+
 def _flag(t, device, what, name):
     if t is None:
         return None
@@ -109,7 +129,99 @@ def _flag(t, device, what, name):
     return t.data_ptr()
 
 
-class SGD(torch.optim.Optimizer):
+class _TableOptimizer(torch.optim.Optimizer):
+    """What ``SGD`` and ``Adam`` share: the table and the whole of ``step()``.  A subclass names itself (``_name``) and its entry
+    point (``_entry``), gives the ctypes type and width of one group's hyper-parameter row (``_hyper_type``, ``_hyper_width``), the
+    group keys an older state dict may lack (``_group_defaults``), and supplies ``_check_group(g)``, ``hyper_row(g)``,
+    ``_state_ptrs(p, g, total)`` and, where the entry takes more arguments, ``_extra()``."""
+
+    _step_supports_amp_scaling = True
+
+    def __init__(self, params, defaults, chunk, max_blocks):
+        self._check_group(defaults)
+        super().__init__(params, defaults)
+        self._reset(chunk, max_blocks)
+
+    def _reset(self, chunk=CHUNK, max_blocks=0):
+        self._table, self._max_blocks = DeviceTable(chunk), int(max_blocks)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for g in self.param_groups:         # a state dict of an older torch, e.g. a reference checkpoint's
+            for k, v in self._group_defaults.items():
+                g.setdefault(k, v)
+        if "_table" not in self.__dict__:
+            self._reset()
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self._check_group(self.param_groups[-1])
+        if len(self.param_groups) > MAX_GROUPS:
+            raise ValueError(f"{self._name}: at most {MAX_GROUPS} param groups (their hyper-parameters travel in the kernel arguments)")
+
+    @property
+    def table_uploads(self):
+        """How often the table went to the device (a step with unchanged tensors uploads nothing)."""
+        return self._table.uploads
+
+    def _zeros_state(self, st, p, key, name):
+        """Device address of ``st[key]``, ``st = state[p]``: created zero-filled in the layout of ``p`` on first use, checked against
+        ``p`` after."""
+        t = st.get(key)
+        if t is None:
+            t = st[key] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        else:
+            _check_tensor(t, p, self._name, name)
+        return t.data_ptr()
+
+    def _extra(self):
+        """The entry's arguments between ``ngroups`` and ``grad_scale``."""
+        return ()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        groups, what, width = self.param_groups, self._name, self._hyper_width
+        errors = (f"{what}: parameters are on {{}}; this package runs on the GPU only (torch.optim.{what} works on these tensors)",
+                  f"{what}: parameters on {{}} and {{}}; one device per optimizer")
+        hyper = (self._hyper_type * (width * len(groups)))()
+        rows, stepped, device, state_ptrs = [], [], None, self._state_ptrs
+        total = sum(len(g["params"]) for g in groups)
+        for j, g in enumerate(groups):
+            self._check_group(g)
+            hyper[width * j:width * (j + 1)] = self.hyper_row(g)
+            for p in g["params"]:
+                grad = p.grad
+                if grad is None:
+                    continue
+                _check_tensor(p, None, what, "a parameter")
+                _check_tensor(grad, p, what, "a gradient")
+                if p.device != device:
+                    device = _one_device(device, p, errors)
+                rows.append((p.data_ptr(), grad.data_ptr(), *state_ptrs(p, g, total), p.numel(), j))
+                stepped.append(p)
+        if not rows:
+            return loss
+        what = what + ".step"
+        grad_scale = _flag(getattr(self, "grad_scale", None), device, what, "grad_scale")
+        found_inf = _flag(getattr(self, "found_inf", None), device, what, "found_inf")
+        rows = np.array(rows, dtype=np.int64)
+        self._table.sync((rows, rows[:, -2]), device)
+        self._last = (hyper, len(groups))
+        self._launch(hyper, len(groups), grad_scale, found_inf)
+        torch.autograd.graph.increment_version(stepped)      # the kernels wrote through raw pointers: Model's caches key on _version
+        return loss
+
+    def _launch(self, hyper, ngroups, grad_scale=None, found_inf=None):
+        """The library call alone, on the table as it is (tools/optim_bench.py times it back to back with ``_last``; for Adam every
+        call counts one more step)."""
+        self._table.call(self._entry, self._max_blocks, hyper, ngroups, *self._extra(), grad_scale, found_inf)
+
+
+class SGD(_TableOptimizer):
     """``torch.optim.SGD`` (dampening = 0, maximize = False) whose ``step()`` is one HIP launch.
 
     Same constructor names, same ``param_groups`` and ``state[p]['momentum_buffer']`` layout: ``state_dict()`` loads into
@@ -120,7 +232,9 @@ class SGD(torch.optim.Optimizer):
     ``buf = grad``, torch's ``clone``), so a first step that ``found_inf`` skips leaves zero buffers in ``state`` where torch leaves
     none.  The next step computes the same values either way."""
 
-    _step_supports_amp_scaling = True
+    _name, _entry = "SGD", "cft_sgd_step"
+    _hyper_type, _hyper_width = ctypes.c_float, 4
+    _group_defaults = dict(nesterov=False, maximize=False, dampening=0, weight_decay=0)
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False, chunk=CHUNK,
                  max_blocks=0):
@@ -132,9 +246,7 @@ class SGD(torch.optim.Optimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=maximize,
                         foreach=None, differentiable=False, fused=None)
-        self._check_group(defaults)
-        super().__init__(params, defaults)
-        self._table, self._max_blocks = DeviceTable(chunk), int(max_blocks)
+        super().__init__(params, defaults, chunk, max_blocks)
 
     @staticmethod
     def _check_group(g):
@@ -145,85 +257,15 @@ class SGD(torch.optim.Optimizer):
         if g.get("nesterov", False) and g.get("momentum", 0) <= 0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
 
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        for g in self.param_groups:         # a state dict of an older torch, e.g. a reference checkpoint's
-            g.setdefault("nesterov", False)
-            g.setdefault("maximize", False)
-            g.setdefault("dampening", 0)
-            g.setdefault("weight_decay", 0)
-        if "_table" not in self.__dict__:
-            self._table, self._max_blocks = DeviceTable(), 0
+    @staticmethod
+    def hyper_row(g):
+        return [float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), 1.0 if g["nesterov"] else 0.0]
 
-    def add_param_group(self, param_group):
-        super().add_param_group(param_group)
-        self._check_group(self.param_groups[-1])
-        if len(self.param_groups) > MAX_GROUPS:
-            raise ValueError(f"SGD: at most {MAX_GROUPS} param groups (their hyper-parameters travel in the kernel arguments)")
-
-    @property
-    def table_uploads(self):
-        """How often the table went to the device (a step with unchanged tensors uploads nothing)."""
-        return self._table.uploads
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        groups = self.param_groups
-        hyper = (ctypes.c_float * (4 * len(groups)))()
-        rows, stepped, device = [], [], None
-        for j, g in enumerate(groups):
-            self._check_group(g)
-            momentum = float(g["momentum"])
-            hyper[4 * j:4 * j + 4] = [float(g["lr"]), momentum, float(g["weight_decay"]), 1.0 if g["nesterov"] else 0.0]
-            for p in g["params"]:
-                grad = p.grad
-                if grad is None:
-                    continue
-                _check_tensor(p, None, "SGD", "a parameter")
-                _check_tensor(grad, p, "SGD", "a gradient")
-                if device is None:
-                    device = p.device
-                    if device.type != "cuda":
-                        raise ValueError(f"SGD: parameters are on {device}; this package runs on the GPU only (torch.optim.SGD works on these tensors)")
-                elif p.device != device:
-                    raise ValueError(f"SGD: parameters on {device} and {p.device}; one device per optimizer")
-                bptr = 0
-                if momentum != 0:
-                    st = self.state[p]
-                    buf = st.get("momentum_buffer")
-                    if buf is None:
-                        buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    else:
-                        _check_tensor(buf, p, "SGD", "a momentum buffer")
-                    bptr = buf.data_ptr()
-                rows.append((p.data_ptr(), grad.data_ptr(), bptr, p.numel(), j))
-                stepped.append(p)
-        if not rows:
-            return loss
-        what = "SGD.step"
-        grad_scale = _flag(getattr(self, "grad_scale", None), device, what, "grad_scale")
-        found_inf = _flag(getattr(self, "found_inf", None), device, what, "found_inf")
-        rows = np.array(rows, dtype=np.int64)
-        self._table.sync((rows, rows[:, 3]), device)
-        self._last = (hyper, len(groups))
-        self._launch(hyper, len(groups), grad_scale, found_inf)
-        torch.autograd.graph.increment_version(stepped)      # the kernel wrote through raw pointers: Model's caches key on _version
-        return loss
-
-    def _launch(self, hyper, ngroups, grad_scale=None, found_inf=None):
-        """The launch alone, on the table as it is (tools/optim_bench.py times it back to back with ``_last``)."""
-        t = self._table
-        with torch.cuda.device(t.device):
-            st = _lib.load().cft_sgd_step(t.dev.data_ptr(), t.host.data_ptr(), t.nseg, t.nwork, t.chunk, self._max_blocks, hyper, ngroups,
-                                          grad_scale, found_inf, torch.cuda.current_stream(t.device).cuda_stream)
-        _lib.check(st, "cft_sgd_step")
+    def _state_ptrs(self, p, g, total):
+        return (self._zeros_state(self.state[p], p, "momentum_buffer", "a momentum buffer") if float(g["momentum"]) != 0 else 0,)
 
 
-class Adam(torch.optim.Optimizer):
+class Adam(_TableOptimizer):
     """``torch.optim.Adam`` (amsgrad = False, maximize = False) whose ``step()`` is one library call: ``cft_adam_step``, two HIP
     launches over every parameter.
 
@@ -237,26 +279,28 @@ class Adam(torch.optim.Optimizer):
     slot and puts the view back - a copy after a load only.  A parameter is counted only in steps in which it has a gradient, as
     in torch.  Moments are created zero-filled on a parameter's first step, also when ``found_inf`` skips it."""
 
-    _step_supports_amp_scaling = True
-    _decoupled = False
-    _name = "Adam"
+    _name, _entry = "Adam", "cft_adam_step"
+    _hyper_type, _hyper_width = ctypes.c_double, 6
+    _group_defaults = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                           decoupled_weight_decay=False)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None, maximize=False,
                  capturable=False, differentiable=False, fused=None, decoupled_weight_decay=None, chunk=CHUNK, max_blocks=0):
+        if decoupled_weight_decay is None:
+            decoupled_weight_decay = self._group_defaults["decoupled_weight_decay"]
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=foreach,
-                        capturable=capturable, differentiable=differentiable, fused=fused,
-                        decoupled_weight_decay=self._decoupled if decoupled_weight_decay is None else bool(decoupled_weight_decay))
-        self._check_group(defaults)
-        super().__init__(params, defaults)
-        self._table, self._max_blocks = DeviceTable(chunk), int(max_blocks)
+                        capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=bool(decoupled_weight_decay))
+        super().__init__(params, defaults, chunk, max_blocks)
+
+    def _reset(self, *table):
+        super()._reset(*table)
         self._steps, self._slot, self._coef = None, {}, None
 
-    @classmethod
-    def _check_group(cls, g):
+    def _check_group(self, g):
         if g.get("amsgrad", False):
-            raise ValueError(f"{cls._name}: amsgrad = False only (the kernel keeps no running maximum)")
+            raise ValueError(f"{self._name}: amsgrad = False only (the kernel keeps no running maximum)")
         if g.get("maximize", False):
-            raise ValueError(f"{cls._name}: maximize = False only")
+            raise ValueError(f"{self._name}: maximize = False only")
         if not 0.0 <= g["lr"]:
             raise ValueError(f"Invalid learning rate: {g['lr']}")
         if not 0.0 <= g["eps"]:
@@ -270,30 +314,10 @@ class Adam(torch.optim.Optimizer):
             if not 0.0 <= betas[k] < 1.0:
                 raise ValueError(f"Invalid beta parameter at index {k}: {betas[k]}")
 
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        for g in self.param_groups:         # a state dict of an older torch, e.g. a reference checkpoint's
-            g.setdefault("amsgrad", False)
-            g.setdefault("maximize", False)
-            g.setdefault("foreach", None)
-            g.setdefault("capturable", False)
-            g.setdefault("differentiable", False)
-            g.setdefault("fused", None)
-            g.setdefault("decoupled_weight_decay", self._decoupled)
-        if "_table" not in self.__dict__:
-            self._table, self._max_blocks = DeviceTable(), 0
-            self._steps, self._slot, self._coef = None, {}, None
-
-    def add_param_group(self, param_group):
-        super().add_param_group(param_group)
-        self._check_group(self.param_groups[-1])
-        if len(self.param_groups) > MAX_GROUPS:
-            raise ValueError(f"{self._name}: at most {MAX_GROUPS} param groups (their hyper-parameters travel in the kernel arguments)")
-
-    @property
-    def table_uploads(self):
-        """How often the table went to the device (a step with unchanged tensors uploads nothing)."""
-        return self._table.uploads
+    @staticmethod
+    def hyper_row(g):
+        beta1, beta2 = g["betas"]
+        return [float(g["lr"]), float(beta1), float(beta2), float(g["eps"]), float(g["weight_decay"]), 1.0 if g["decoupled_weight_decay"] else 0.0]
 
     def _step_slot(self, p, device, total):
         """Device address of the step counter of ``p`` (one of ``total`` parameters in the groups); ``state[p]['step']`` is (again)
@@ -323,75 +347,23 @@ class Adam(torch.optim.Optimizer):
         st["step"] = slot
         return ptr
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        groups, what = self.param_groups, self._name
-        hyper = (ctypes.c_double * (6 * len(groups)))()
-        rows, stepped, device = [], [], None
-        total = sum(len(g["params"]) for g in groups)
-        for j, g in enumerate(groups):
-            self._check_group(g)
-            beta1, beta2 = g["betas"]
-            hyper[6 * j:6 * j + 6] = [float(g["lr"]), float(beta1), float(beta2), float(g["eps"]), float(g["weight_decay"]),
-                                      1.0 if g["decoupled_weight_decay"] else 0.0]
-            for p in g["params"]:
-                grad = p.grad
-                if grad is None:
-                    continue
-                _check_tensor(p, None, what, "a parameter")
-                _check_tensor(grad, p, what, "a gradient")
-                if device is None:
-                    device = p.device
-                    if device.type != "cuda":
-                        raise ValueError(f"{what}: parameters are on {device}; this package runs on the GPU only (torch.optim.{what} works on these tensors)")
-                elif p.device != device:
-                    raise ValueError(f"{what}: parameters on {device} and {p.device}; one device per optimizer")
-                st = self.state[p]
-                m, v = st.get("exp_avg"), st.get("exp_avg_sq")
-                if m is None:
-                    m = st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                else:
-                    _check_tensor(m, p, what, "exp_avg")
-                if v is None:
-                    v = st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                else:
-                    _check_tensor(v, p, what, "exp_avg_sq")
-                rows.append((p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), self._step_slot(p, device, total), p.numel(), j))
-                stepped.append(p)
-        if not rows:
-            return loss
-        what = what + ".step"
-        grad_scale = _flag(getattr(self, "grad_scale", None), device, what, "grad_scale")
-        found_inf = _flag(getattr(self, "found_inf", None), device, what, "found_inf")
-        rows = np.array(rows, dtype=np.int64)
-        self._table.sync((rows, rows[:, 5]), device)
-        if self._coef is None or self._coef.device != device or self._coef.shape[0] < len(rows):
-            self._coef = torch.empty((len(rows), 2), dtype=torch.float32, device=device)      # per tensor: step_size, sqrt(bias correction 2)
-        self._last = (hyper, len(groups))
-        self._launch(hyper, len(groups), grad_scale, found_inf)
-        torch.autograd.graph.increment_version(stepped)      # the kernels wrote through raw pointers: Model's caches key on _version
-        return loss
+    def _state_ptrs(self, p, g, total):
+        st = self.state[p]
+        return (self._zeros_state(st, p, "exp_avg", "exp_avg"), self._zeros_state(st, p, "exp_avg_sq", "exp_avg_sq"), self._step_slot(p, p.device, total))
 
-    def _launch(self, hyper, ngroups, grad_scale=None, found_inf=None):
-        """The library call alone, on the table as it is (tools/optim_bench.py times it back to back with ``_last``; every call
-        counts one more step)."""
+    def _extra(self):
         t = self._table
-        with torch.cuda.device(t.device):
-            st = _lib.load().cft_adam_step(t.dev.data_ptr(), t.host.data_ptr(), t.nseg, t.nwork, t.chunk, self._max_blocks, hyper, ngroups,
-                                           self._coef.data_ptr(), grad_scale, found_inf, torch.cuda.current_stream(t.device).cuda_stream)
-        _lib.check(st, "cft_adam_step")
+        if self._coef is None or self._coef.device != t.device or self._coef.shape[0] < t.nseg:
+            self._coef = torch.empty((t.nseg, 2), dtype=torch.float32, device=t.device)      # per tensor: step_size, sqrt(bias correction 2)
+        return (self._coef.data_ptr(),)
 
 
 class AdamW(Adam):
     """``torch.optim.AdamW``: ``Adam`` with ``weight_decay = 1e-2`` and the decay decoupled from the gradient
     (``p *= 1 - lr * weight_decay`` before the update) by default."""
 
-    _decoupled = True
     _name = "AdamW"
+    _group_defaults = dict(Adam._group_defaults, decoupled_weight_decay=True)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)

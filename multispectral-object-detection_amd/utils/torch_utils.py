@@ -7,9 +7,10 @@ from copy import deepcopy
 import numpy as np
 import torch
 
-from .. import _lib
 from ..models.common import invalidate_packed
-from .optim import CHUNK, DeviceTable, _check_tensor
+from .optim import CHUNK, DeviceTable, _check_tensor, _one_device
+
+_DEVICE_ERRORS = ("ModelEMA: the model is on {}; this package runs on the GPU only", "ModelEMA: tensors on {} and {}")
 
 # what Model and its modules keep in __dict__ besides their state: packed weights, launch plans, captured graphs, the tensor list of
 # weights_key, the layer graph, the side stream.  None of it can or should be copied; all of it is rebuilt on demand.
@@ -78,12 +79,8 @@ class ModelEMA:
             m = msd[k]
             _check_tensor(v, None, "ModelEMA", f"ema {k}")
             _check_tensor(m, v, "ModelEMA", f"model {k}")
-            if device is None:
-                device = v.device
-                if device.type != "cuda":
-                    raise ValueError(f"ModelEMA: the model is on {device}; this package runs on the GPU only")
-            elif v.device != device:
-                raise ValueError(f"ModelEMA: tensors on {device} and {v.device}")
+            if v.device != device:
+                device = _one_device(device, v, _DEVICE_ERRORS)
             rows.append((v.data_ptr(), m.data_ptr(), v.numel()))
             written.append(v)
         if not rows:
@@ -96,11 +93,7 @@ class ModelEMA:
     def _launch(self, d):
         """The launch alone, on the table as it is.  d and 1 - d are each computed in double, then rounded to float: what
         ``v *= d; v += (1. - d) * msd[k]`` does with Python scalars."""
-        t = self._table
-        with torch.cuda.device(t.device):
-            st = _lib.load().cft_ema_update(t.dev.data_ptr(), t.host.data_ptr(), t.nseg, t.nwork, t.chunk, self._max_blocks, ctypes.c_float(d),
-                                            ctypes.c_float(1. - d), torch.cuda.current_stream(t.device).cuda_stream)
-        _lib.check(st, "cft_ema_update")
+        self._table.call("cft_ema_update", self._max_blocks, ctypes.c_float(d), ctypes.c_float(1. - d))
 
     def update_attr(self, model, include=(), exclude=('process_group', 'reducer')):
         copy_attr(self.ema, model, include, exclude)

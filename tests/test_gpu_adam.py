@@ -78,8 +78,8 @@ class _Hyp:
         self.eps = [eps, eps * 10, eps * 0.5]
         self.wd = [wd, wd * 2, 0.0]
 
-    def make(self, cls, groups):
-        opt = cls(groups[0], lr=self.lr[0], betas=self.betas[0], eps=self.eps[0], weight_decay=self.wd[0])
+    def make(self, cls, groups, **kw):
+        opt = cls(groups[0], lr=self.lr[0], betas=self.betas[0], eps=self.eps[0], weight_decay=self.wd[0], **kw)
         for k in (1, 2):
             opt.add_param_group({"params": groups[k], "lr": self.lr[k], "betas": self.betas[k], "eps": self.eps[k], "weight_decay": self.wd[k]})
         return opt
@@ -167,6 +167,35 @@ def test_adam_numerics(dev, decoupled, wd, beta1, eps):
         for x, y in zip(a[0] + a[1] + a[2], b[0] + b[1] + b[2]):
             assert torch.equal(x, y)
         assert a[3] == b[3]
+
+
+def test_cut_and_grid_do_not_change_the_result(dev):
+    """The rule is per element, so neither the cut of the table nor the number of workgroups that walk it can show in the result:
+    chunk 1024 on two workgroups (33 work rows: both workgroups wrap many times, the chunk boundaries fall elsewhere) gives, bit
+    for bit, the parameters, moments and step counts that the defaults give - and stays within the oracle's bound."""
+    optim = _mods()[0]
+    hyp = _Hyp()
+
+    def run(cls, **cut):
+        ps = _Params(dev, optim.CHUNK)
+        opt = hyp.make(cls, ps.groups(), **cut)
+        trail = []
+        for step in range(3):
+            before = _snapshot(ps, opt)
+            grads = ps.new_grads(step)
+            opt.step()
+            trail.append(_snapshot(ps, opt))
+            if cut:
+                _check_step(f"{cls.__name__}, chunk 1024, 2 workgroups, step {step + 1}", ps, before, trail[-1], grads, hyp, cls is optim.AdamW,
+                            [step + 1.0] * len(ps.params))
+        return trail, opt._table
+
+    for cls in (optim.Adam, optim.AdamW):
+        (want, table), (got, cut_table) = run(cls), run(cls, chunk=1024, max_blocks=2)
+        assert (table.chunk, cut_table.chunk) == (optim.CHUNK, 1024) and cut_table.nwork == 33 > table.nwork
+        for step, (a, b) in enumerate(zip(want, got)):
+            assert all(torch.equal(x, y) for x, y in zip(a[0] + a[1] + a[2], b[0] + b[1] + b[2]))
+            assert a[3] == b[3] == [step + 1.0] * len(a[3])
 
 
 def test_step_counts_are_per_tensor(dev):

@@ -64,8 +64,8 @@ class _Params:
             p.grad = (_randn(self.rng, p.numel()) * scale).to(p.device)
 
 
-def _make(optim_cls, groups, lrs, moms, wds, nesterov):
-    opt = optim_cls(groups[0], lr=lrs[0], momentum=moms[0], weight_decay=wds[0], nesterov=nesterov)
+def _make(optim_cls, groups, lrs, moms, wds, nesterov, **kw):
+    opt = optim_cls(groups[0], lr=lrs[0], momentum=moms[0], weight_decay=wds[0], nesterov=nesterov, **kw)
     for k in (1, 2):
         opt.add_param_group({"params": groups[k], "lr": lrs[k], "momentum": moms[k], "weight_decay": wds[k]})
     return opt
@@ -139,6 +139,56 @@ def test_sgd_numerics(dev, nesterov, wd, momentum):
     for a, b in zip(first, second):                                                            # the same run to run, bit for bit
         for x, y in zip(a[0] + [t for t in a[1] if t is not None], b[0] + [t for t in b[1] if t is not None]):
             assert torch.equal(x, y)
+
+
+def test_cut_and_grid_do_not_change_the_result(dev):
+    """The rule is per element, so neither the cut of the table nor the number of workgroups that walk it can show in the result:
+    chunk 1024 on two workgroups (33 work rows for the step, 11 for the EMA: every workgroup wraps, the chunk boundaries fall
+    elsewhere) gives, bit for bit, what the defaults give - and stays within the oracle's bound.  Group 1 has no momentum: the
+    walk's absent stream."""
+    optim, torch_utils, _ = _mods()
+    lrs, moms, wds = (0.01, 0.02, 0.1), (0.937, 0.0, 0.5), (0.0, 5e-4, 0.0)
+
+    def sgd(**cut):
+        ps = _Params(dev, optim.CHUNK)
+        opt = _make(optim.SGD, ps.groups(), lrs, moms, wds, False, **cut)
+        trail = []
+        for step in range(3):
+            ps.new_grads()
+            before, grads = _snapshot(ps, opt), [p.grad.cpu().clone() for p in ps.params]
+            opt.step()
+            trail.append(_snapshot(ps, opt))
+            if cut:
+                _check_step(f"chunk 1024, 2 workgroups, step {step}", ps, before, trail[-1], grads, (lrs, moms, wds), False)
+        return trail, opt._table
+
+    def ema(cut):
+        net = R.SmallNet().to(dev)
+        net.load_state_dict(R.seeded_state(net, 0))
+        avg = torch_utils.ModelEMA(net, updates=2000)                             # decay 0.63: both terms of the rule count
+        if cut:
+            avg._table, avg._max_blocks = optim.DeviceTable(1024), 2
+        trail = [{name: v.cpu().clone() for name, v in avg.ema.state_dict().items()}]
+        for k in (1, 2, 3):
+            model = R.seeded_state(net, k)
+            net.load_state_dict(model)
+            avg.update(net)
+            trail.append({name: v.cpu().clone() for name, v in avg.ema.state_dict().items()})
+            for name, v in trail[-1].items():
+                if cut and v.dtype.is_floating_point:
+                    ref, bound = R.ema_update(trail[-2][name], model[name], avg.decay(avg.updates))
+                    assert R.worst(v, ref, bound) <= 1.0, (k, name)
+        return trail, avg._table
+
+    (want, table), (got, cut_table) = sgd(), sgd(chunk=1024, max_blocks=2)
+    assert (table.chunk, cut_table.chunk) == (optim.CHUNK, 1024) and cut_table.nwork == 33 > table.nwork
+    for a, b in zip(want, got):
+        for x, y in zip(a[0] + a[1], b[0] + b[1]):
+            assert (x is None and y is None) if x is None or y is None else torch.equal(x, y)
+    (want, table), (got, cut_table) = ema(False), ema(True)
+    assert (table.chunk, cut_table.chunk) == (optim.CHUNK, 1024) and cut_table.nwork == 11 > table.nwork
+    for a, b in zip(want, got):
+        assert a.keys() == b.keys() and all(torch.equal(a[k], b[k]) for k in a)
 
 
 def test_one_launch_no_synchronise(dev, golden):
