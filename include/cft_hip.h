@@ -368,6 +368,79 @@ int cft_jpeg_info(const unsigned char* bytes, long nbytes, cft_jpeg_info_t* info
 int cft_jpeg_entropy(const unsigned char* bytes, long nbytes, short* coef, unsigned short* qtab, const cft_jpeg_info_t* info);
 int cft_jpeg_decode_u8(const void* table_dev, const void* table_host, int n, void* workspace, long workspace_bytes, void* stream);
 
+/*
+ * Baseline JPEG ENCODING, the decoder's two halves in the other direction (csrc/jpeg_encode.hip; no reference counterpart: the
+ * reference writes its files with cv2.imwrite).  The yardstick is PIL, Image.fromarray(a).save(f, 'JPEG', quality=q, subsampling=s)
+ * with optimize off (libjpeg-turbo, JDCT_ISLOW, the standard Huffman tables): the device half is checked on quantised coefficients
+ * (cft_jpeg_entropy of PIL's file), the whole file on bytes.  All arithmetic is integer, every shift arithmetic.
+ *   1. Colour (3 components): Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ *      Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ *      One component: the grey byte is Y.
+ *   2. Edges and downsampling.  A full-resolution sample outside the image is the nearest one inside: x clamped to width - 1, y to
+ *      height - 1.  A component halved horizontally (h2v1) is out[i] = (in[2i] + in[2i+1] + bias) >> 1 with bias 0, 1, 0, 1 ... by
+ *      output column i; halved both ways (h2v2) out[i] = (the 2 x 2 samples + bias) >> 2 with bias 1, 2, 1, 2 ...  Columns are NOT clamped
+ *      to the downsampled width cw: the padded column i >= cw averages clamped full-resolution samples with its own bias.  Rows are:
+ *      a row >= ch = ceil(height * v / vmax) of a component repeats its last DOWNSAMPLED row ch - 1 (for an even height that is the
+ *      mean of the last two rows, not the last row).
+ *   3. Forward DCT: libjpeg's jpeg_fdct_islow on samples - 128 (CONST_BITS 13, PASS1_BITS 2, the twelve FIX constants of the decoder
+ *      above, the published butterfly).  Rows first: outputs 0 and 4 are (sum) << 2, the others DESCALE(x, 11); then columns: outputs
+ *      0 and 4 are DESCALE(x, 2), the others DESCALE(x, 15).  DESCALE(x, n) = (x + (1 << (n-1))) >> n.  The result is 8 x the DCT.
+ *   4. Quantise: d = q << 3, coef = sign(c) * ((|c| + (d >> 1)) / d), the division truncating (done as an unsigned integer division).
+ *   5. Tables: scale = quality < 50 ? 5000 / quality : 200 - 2 quality, q = clamp((base * scale + 50) / 100, 1, 255) over the luminance
+ *      and chrominance tables of ITU T.81 Annex K, quality 1..100.  The four Huffman tables are Annex K's.
+ *   6. Dummy blocks: a block of the MCU-padded grid bw x bh outside the component's real grid ceil(cw / 8) x ceil(ch / 8) is not
+ *      transformed; it is coded with all AC zero and the DC of the previous block of its component in MCU order (a DC difference of
+ *      0).  Only luma has them, under subsampling.  The device writes 64 zeros there, the writer ignores what the buffer holds there.
+ *   7. File: SOI, APP0 JFIF 1.01 (units 0, density 1 x 1, no thumbnail), DQT luma, DQT chroma (3 components only), SOF0 (component ids
+ *      1 2 3, chroma sampled 1x1 on table 1), DHT DC0, AC0, DC1, AC1 (one component: DC0, AC0), SOS, one interleaved scan without
+ *      restart markers, 0xFF bytes stuffed, the last byte padded with 1-bits, EOI.
+ *
+ * HOST half - plain C++, no HIP call, re-entrant as the decoder's host half is (nothing shared is written, not even cft_last_error's
+ * text).  Sampling is the decoder's subset: 1 component 1x1; 3 components with luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0).
+ *   cft_jpeg_layout(width, height, ncomp, hmax, vmax, info): the cft_jpeg_info_t of a file to be written (what cft_jpeg_info reports
+ *     for PIL's file of that geometry; restart_interval 0).  CFT_EINVAL: null info, sides outside 1..CFT_JPEG_MAX_SIDE, other sampling.
+ *   cft_jpeg_quality_tables(quality, qtab): uint16 [3][64] in natural order, row 0 luminance, rows 1 and 2 chrominance.  CFT_EINVAL:
+ *     null pointer, quality outside 1..100.
+ *   cft_jpeg_write_bound(info, bound): *bound receives a byte count no file of that geometry exceeds (headers + 416 bytes per block:
+ *     63 AC symbols of 16 + 10 bits and a DC of 11 + 11 bits, every byte stuffed; beyond 2^31 for the largest sides, hence a long).
+ *     CFT_EINVAL, with *bound = -1, for a null pointer or an info that cft_jpeg_layout would not have produced.
+ *   cft_jpeg_write(coef, qtab, info, out, cap, nbytes): headers and Huffman coding of coef (the layout cft_jpeg_entropy writes and
+ *     cft_jpeg_encode_coef produces) into out[0, cap); *nbytes receives the file size.  Never writes at or past out + cap.  Return:
+ *     CFT_OK; CFT_EINVAL (null pointer, info that cft_jpeg_layout would not have produced, a table entry outside 1..255 or chroma rows
+ *     that differ, cap < 0); CFT_JPEG_SHORT_BUFFER (cap too small: *nbytes is 0, out holds a prefix); CFT_JPEG_UNSUPPORTED (a
+ *     coefficient baseline coding cannot hold: an AC value beyond 10 bits or a DC difference beyond 11).
+ *
+ * DEVICE half - cft_jpeg_encode_coef turns n images of mixed sizes into quantised coefficients in ONE launch, grid (blocks of the
+ * largest image / 32, image): jpeg_fdct_kernel, 8 lanes per 8x8 block of the padded grids of all components; lane r gathers row r of
+ * its block straight from the source (colour conversion and downsampling on the way, indices clamped as in 2.), transforms it, the
+ * block is transposed through LDS (72-dword block stride), lane c transforms and quantises column c, a second LDS transpose hands
+ * lane r the 8 coefficients of row r, stored as one 16-byte word.  No plane workspace, no atomics, no inline assembly; every
+ * coefficient of the padded grid is written once (dummy blocks as zeros).  table_dev / table_host hold one cft_jpeg_enc_desc_t per
+ * image (device copy / host copy of the same bytes).  Every row of the host copy is checked before the launch and nothing is
+ * launched on CFT_EINVAL: null pointers, misaligned ones (tables 8, coef 16, qtab and qtab_host 2), 1 <= n <= 65535, sides
+ * 1..CFT_JPEG_MAX_SIDE, sampling in the subset, src_stride >= ncomp * width, bw / bh equal to the padded grid, every entry of
+ * qtab_host rows < ncomp in 1..255.  The kernel clamps its own indices as well and treats a zero divisor as 1.
+ * src: HWC uint8, RGB or one channel, pixel (y, x) at src + y * src_stride + ncomp * x; it is only read.
+ */
+#define CFT_JPEG_SHORT_BUFFER 2
+#define CFT_JPEG_ENC_DESC_BYTES 96
+typedef struct {
+  const unsigned char* src;       /* device: HWC uint8, 3 channels RGB or 1 */
+  const unsigned short* qtab;     /* device: uint16 [3][64], natural order */
+  const unsigned short* qtab_host;/* host: the same tables, what the guards read */
+  short* coef;                    /* device: 64 * sum bw * bh int16, 16-byte aligned */
+  long src_stride;                /* bytes per row of src, >= ncomp * width */
+  int width, height;
+  int ncomp, hmax, vmax;
+  int bw[3], bh[3];
+  int reserved[3];
+} cft_jpeg_enc_desc_t;
+int cft_jpeg_layout(int width, int height, int ncomp, int hmax, int vmax, cft_jpeg_info_t* info);
+int cft_jpeg_quality_tables(int quality, unsigned short* qtab);
+int cft_jpeg_write_bound(const cft_jpeg_info_t* info, long* bound);
+int cft_jpeg_write(const short* coef, const unsigned short* qtab, const cft_jpeg_info_t* info, unsigned char* out, long cap, long* nbytes);
+int cft_jpeg_encode_coef(const void* table_dev, const void* table_host, int n, void* stream);
+
 /* Elementwise out = a + b over M pixels x C channels (Add / Add2, models/common.py:228-243). */
 int cft_add(const void* a, int lda, int aoff, const void* b, int ldb, int boff,
             void* out, int ldo, int ooff, long M, int C, int dtype, void* stream);

@@ -16,7 +16,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: experiments with an alternative build, e.g. the probe library)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip")
+SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip", "jpeg_encode.hip")
 
 HEADER = os.path.join(_HERE, "..", "include", "cft_hip.h")
 HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "resize_common.h", "conv_gemm_asm.inc")
@@ -62,12 +62,20 @@ ACT_NONE, ACT_SILU, ACT_GELU = (_consts[k] for k in ("CFT_ACT_NONE", "CFT_ACT_SI
 _lib = None
 
 
+def missing_symbols():
+    """The entry points of the header that the built library's bytes do not name (its dynamic string table holds every export): a
+    library from before an entry point was added is stale whatever its timestamp says.  Nothing is loaded."""
+    with open(LIB_PATH, "rb") as fh:
+        blob = fh.read()
+    return [name for name in SIGNATURES if name.encode() + b"\0" not in blob]
+
+
 def build(verbose=False):
     """Compile every HIP source for gfx950 into ``libcft_hip.so`` next to this file."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER]
     newest = max(os.path.getmtime(p) for p in srcs + hdrs)
-    if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
+    if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest and not missing_symbols():
         return LIB_PATH
     # one object per source, compiled concurrently (only the stale ones), then one link
     hdr_time = max(os.path.getmtime(h) for h in hdrs)

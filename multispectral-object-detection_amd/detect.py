@@ -21,6 +21,7 @@ import torch
 from .ops import detect_boxes
 from .utils.datasets import LoadImagePairs, MAX_DECODE_THREADS
 from .utils.general import batched_nms, increment_path, save_one_box
+from .utils.jpeg import encode_jpeg_start, is_jpeg_name
 from .utils.metrics import _to_device, geometry, txt_line
 from .utils.plots import BoxRenderer
 
@@ -79,6 +80,13 @@ def _save_image(path, array):
     Image.fromarray(array).save(path)
 
 
+def _save_jpeg(path, job, k):
+    """Pool job of ``device_jpeg``: wait for the batch's coefficient copy, code image ``k`` of the job, write the file."""
+    data = job.file_bytes(k)
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
 def boxes_and_render(dets, counts, shapes, img_hw, originals, renderer, nc):
     """The device stage of one batch: ``cft_detect_boxes`` and, with a ``renderer``, ``cft_detect_render`` into ``originals``.  Returns
     ``(boxes, hist, flag)`` on the device.  No synchronisation with the host."""
@@ -91,7 +99,11 @@ def boxes_and_render(dets, counts, shapes, img_hw, originals, renderer, nc):
 
 def detect(opt, model=None, log=print, record=None):
     """``detect(opt)`` of detect_twostream.py:19-194.  ``model``: an already loaded model instead of ``opt.weights``.  ``record``: a list
-    that receives, per image, a dict of what was computed (paths, NMS output, box buffer, printed line) - for tests and callers."""
+    that receives, per image, a dict of what was computed (paths, NMS output, box buffer, printed line) - for tests and callers.
+
+    ``opt.device_jpeg`` (absent = False): saved images whose name ends in .jpg / .jpeg are encoded by ``utils.jpeg.encode_jpeg_start`` -
+    colour conversion, DCT and quantisation on the device, Huffman coding on the pool - to the bytes PIL writes for them; the drawn
+    originals are then copied to the host only for ``record`` or for files of another suffix, which stay on PIL."""
     check_options(opt)
     source1, source2, save_txt, imgsz = opt.source1, opt.source2, opt.save_txt, opt.img_size
     save_img = not opt.nosave                                                     # (.txt sources are refused above)
@@ -117,6 +129,7 @@ def detect(opt, model=None, log=print, record=None):
 
     dataset = LoadImagePairs(source1, source2, imgsz, stride, batch_size=opt.batch_size, device=device)
     draw = save_img                                                               # boxes are drawn only into images that are saved
+    device_jpeg = bool(getattr(opt, 'device_jpeg', False)) and save_img
     renderer = BoxRenderer(names, device, opt.line_thickness, opt.hide_labels, opt.hide_conf) if draw else None
 
     t0 = time.time()
@@ -131,6 +144,11 @@ def detect(opt, model=None, log=print, record=None):
                 dets, counts = batched_nms(pred, opt.conf_thres, opt.iou_thres, classes=opt.classes, agnostic=opt.agnostic_nms, max_det=MAX_DET)
             undrawn = [o[0] for o in dataset.host_originals]                      # crops are cut from the undrawn original, on the host
             boxes, hist, flag = boxes_and_render(dets, counts, shapes, (H, W), originals, renderer, nc)
+            on_device = [device_jpeg and is_jpeg_name(paths[b][0]) for b in range(B)]
+            job, job_slot = None, {}
+            if any(on_device):                                                    # started before the box buffer's copy waits for the device
+                job_slot = {b: 2 * k for k, b in enumerate(b for b in range(B) if on_device[b])}
+                job = encode_jpeg_start([o for b in job_slot for o in originals[b]])
             n_words = boxes.numel()
             packed = torch.cat((boxes.view(-1), hist.view(-1), flag.view(-1))).cpu().numpy()   # the one copy of the box buffer
             t2 = time.time()
@@ -139,7 +157,7 @@ def detect(opt, model=None, log=print, record=None):
             if packed[-1]:
                 raise RuntimeError(f"detect: a detection's class is outside [0, {nc}) - the model's names do not match its head")
             drawn = None
-            if save_img:
+            if save_img and (record is not None or not all(on_device)):
                 drawn = torch.stack([torch.stack(o) for o in originals]).cpu().numpy()     # one copy of the drawn originals (one size per batch)
             for b in range(B):
                 p = Path(paths[b][0])
@@ -163,8 +181,12 @@ def detect(opt, model=None, log=print, record=None):
                     save_path = str(save_dir / p.name)
                     stem, ext = save_path.rsplit('.', 1) if '.' in p.name else (save_path, 'jpg')
                     log(stem + '_rgb.' + ext)
-                    jobs.append(pool.submit(_save_image, stem + '_rgb.' + ext, drawn[b, 0]))
-                    jobs.append(pool.submit(_save_image, stem + '_ir.' + ext, drawn[b, 1]))
+                    if on_device[b]:
+                        jobs.append(pool.submit(_save_jpeg, stem + '_rgb.' + ext, job, job_slot[b]))
+                        jobs.append(pool.submit(_save_jpeg, stem + '_ir.' + ext, job, job_slot[b] + 1))
+                    else:
+                        jobs.append(pool.submit(_save_image, stem + '_rgb.' + ext, drawn[b, 0]))
+                        jobs.append(pool.submit(_save_image, stem + '_ir.' + ext, drawn[b, 1]))
                 if record is not None:
                     record.append({"paths": paths[b], "shape": shapes[b][0], "img_hw": (H, W), "dets": dets[b, :n].cpu(), "slots": slots[b].copy(),
                                    "hist": hists[b].copy(), "s": s, "drawn": None if drawn is None else drawn[b].copy()})

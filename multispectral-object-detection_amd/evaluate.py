@@ -72,20 +72,41 @@ def _save_mosaics(host, event, flag, files):
         save_mosaic(a.numpy(), f)
 
 
-def _plot_batch(pool, img, targets, paths, fname, names):
-    """One mosaic (both streams) on the device, then its copies to pinned memory; the wait and the encoding go to the pool."""
+def _save_mosaics_coded(job, event, flag, files):
+    """Pool job of ``plots`` with ``device_jpeg``: wait for the flag word and the coefficients, Huffman-code, write the files."""
+    from .utils.plots import check_mosaic_flag
+    event.synchronize()
+    if flag is not None:
+        check_mosaic_flag(int(flag[0]))
+    for k, f in enumerate(files):
+        data = job.file_bytes(k)
+        with open(f, 'wb') as fh:
+            fh.write(data)
+
+
+def _plot_batch(pool, img, targets, paths, fname, names, device_jpeg=False):
+    """One mosaic (both streams) on the device, then its copies to pinned memory; the wait and the encoding go to the pool.  With
+    ``device_jpeg`` and a .jpg / .jpeg name what is copied are the quantised coefficients of the device encoder, not the pixels."""
+    from .utils.jpeg import encode_jpeg_start, is_jpeg_name
     from .utils.plots import mosaic_file_names, plot_images_device
     mosaics, flag, _ = plot_images_device(img, targets, paths, names)
-    host = [torch.empty(m.shape, dtype=m.dtype).pin_memory().copy_(m, non_blocking=True) for m in mosaics]
+    coded = device_jpeg and is_jpeg_name(fname)
+    if coded:
+        job = encode_jpeg_start(list(mosaics))
+    else:
+        host = [torch.empty(m.shape, dtype=m.dtype).pin_memory().copy_(m, non_blocking=True) for m in mosaics]
     if flag is not None:
         flag = torch.empty(1, dtype=torch.int32).pin_memory().copy_(flag, non_blocking=True)
     event = torch.cuda.Event()
     event.record()
+    if coded:
+        return pool.submit(_save_mosaics_coded, job, event, flag, mosaic_file_names(fname, len(job)))
     return pool.submit(_save_mosaics, host, event, flag, mosaic_file_names(fname, len(host)))
 
 
 def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None, confusion=False,
-             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None, plots=False, names=None):
+             save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None, plots=False, names=None,
+             device_jpeg=False):
     """batches: an iterable of ``(img6_uint8 [B, 6, H, W], targets [nt, 6], paths, shapes)`` as test.py's dataloader yields.
     Returns test.py's ``((mp, mr, map50, map75, map), maps)``; with ``compute_loss``, test.py's
     ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches.
@@ -95,6 +116,8 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
 
     ``plots`` (needs a ``save_dir``): the label and prediction mosaics of the first three batches, both streams (module docstring), with
     the class ``names`` (None: class numbers); the files are complete when this returns.  It adds no element to the return value.
+    ``device_jpeg``: the mosaics are encoded by ``utils.jpeg.encode_jpeg_start`` (device DCT, Huffman coding on the same pool) instead
+    of by PIL; the files hold the same bytes.
 
     ``details``: a dict that receives ``"result"``, the ``EvalResult`` behind the returned tuple (per-class p / r / ap, nt, seen - what
     test.py's table prints, tools/val.py); the return value does not change."""
@@ -134,12 +157,12 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
             dets, counts = batched_nms(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls)
         ev.update(dets, counts, targets, (H, W), shapes)
         if plots and nb < 3:                                               # test.py:220-225
-            jobs.append(_plot_batch(pool, img, targets, paths, Path(save_dir) / f'test_batch{nb}_labels.jpg', names))
+            jobs.append(_plot_batch(pool, img, targets, paths, Path(save_dir) / f'test_batch{nb}_labels.jpg', names, device_jpeg))
             pd = dets
             if single_cls:                                                 # test.py:146-147 zeroes the class in place before it plots `out`
                 pd = dets.clone()
                 pd[..., 5] = 0
-            jobs.append(_plot_batch(pool, img, (pd, counts), paths, Path(save_dir) / f'test_batch{nb}_pred.jpg', names))
+            jobs.append(_plot_batch(pool, img, (pd, counts), paths, Path(save_dir) / f'test_batch{nb}_pred.jpg', names, device_jpeg))
         if save_txt or save_json:
             for stem, rows in export_rows(export_batch(dets, counts, (H, W), shapes, single_cls), paths):
                 if save_txt:

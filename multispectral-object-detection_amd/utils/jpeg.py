@@ -1,8 +1,14 @@
 """Baseline JPEG decoding with the entropy half on the host and the pixel half on the device (csrc/jpeg.hip, defined in
 include/cft_hip.h): ``jpeg_info`` / ``jpeg_entropy`` wrap the two host functions - plain C++, callable without a GPU and from many
 threads at once - and ``decode_jpeg_batch`` decodes a list of files with one upload and one ``cft_jpeg_decode_u8`` call (two launches).
-A file outside the supported subset is reported as such, never decoded approximately: the caller hands it to PIL."""
+A file outside the supported subset is reported as such, never decoded approximately: the caller hands it to PIL.
+
+Encoding is the same seam in the other direction (csrc/jpeg_encode.hip): ``encode_jpeg_batch`` turns device images into the bytes
+PIL's ``save(f, 'JPEG', quality=q, subsampling=s)`` writes - one table upload, one ``cft_jpeg_encode_coef`` launch, one non-blocking copy
+of the coefficients into pinned memory, then ``cft_jpeg_write`` (headers and Huffman coding) on a pool of host threads;
+``encode_jpeg_start`` / ``EncodeJob`` is the form that lets a caller overlap the copy and the coding with other work."""
 import ctypes
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -20,6 +26,14 @@ JPEG_INFO = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("h
 JPEG_DESC = np.dtype([("coef", "<u8"), ("qtab", "<u8"), ("dst", "<u8"), ("dst_stride", "<i8"), ("plane_off", "<i8"), ("width", "<i4"), ("height", "<i4"),
                       ("ncomp", "<i4"), ("hmax", "<i4"), ("vmax", "<i4"), ("bw", "<i4", (3,)), ("bh", "<i4", (3,)), ("reserved", "<i4", (3,))])
 assert JPEG_INFO.itemsize == _lib._consts["CFT_JPEG_INFO_BYTES"] and JPEG_DESC.itemsize == _lib._consts["CFT_JPEG_DESC_BYTES"]
+# one row of the table cft_jpeg_encode_coef reads: cft_jpeg_enc_desc_t of include/cft_hip.h
+JPEG_ENC_DESC = np.dtype([("src", "<u8"), ("qtab", "<u8"), ("qtab_host", "<u8"), ("coef", "<u8"), ("src_stride", "<i8"), ("width", "<i4"), ("height", "<i4"),
+                          ("ncomp", "<i4"), ("hmax", "<i4"), ("vmax", "<i4"), ("bw", "<i4", (3,)), ("bh", "<i4", (3,)), ("reserved", "<i4", (3,))])
+assert JPEG_ENC_DESC.itemsize == _lib._consts["CFT_JPEG_ENC_DESC_BYTES"]
+SHORT_BUFFER = _lib._consts["CFT_JPEG_SHORT_BUFFER"]
+SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2), 0: (1, 1), 1: (2, 1), 2: (2, 2)}      # luma (hmax, vmax); the integers are PIL's
+MAX_ENCODE_THREADS = 16
+JPEG_SUFFIXES = (".jpg", ".jpeg")
 
 
 def _align16(n):
@@ -136,3 +150,158 @@ def decode_jpeg_batch(blobs, device, out=None):
         table_dev = table_host.to(device, non_blocking=True)
         jpeg_decode_u8(table_dev, table_host, len(live), workspace)
     return results
+
+
+# ---------------------------------------------------------------------------------------------------------------- encoding
+def jpeg_layout(width, height, ncomp, hmax=1, vmax=1):
+    """``cft_jpeg_layout``: the JPEG_INFO record of a file to be written.  Needs no GPU."""
+    info = np.zeros((), dtype=JPEG_INFO)
+    if _lib.load().cft_jpeg_layout(int(width), int(height), int(ncomp), int(hmax), int(vmax), info.ctypes.data) != OK:
+        raise ValueError(f"jpeg_layout: {width} x {height}, {ncomp} component(s) sampled {hmax}x{vmax} is outside what the encoder writes "
+                         f"(sides 1..{MAX_SIDE}; grey 1x1, colour 1x1 / 2x1 / 2x2)")
+    return info
+
+
+def jpeg_quality_tables(quality):
+    """``cft_jpeg_quality_tables``: uint16 [3, 64], natural order, rows luminance / chrominance / chrominance.  Needs no GPU."""
+    qtab = np.zeros((3, 64), dtype=np.uint16)
+    if _lib.load().cft_jpeg_quality_tables(int(quality), qtab.ctypes.data) != OK:
+        raise ValueError(f"jpeg_quality_tables: quality {quality} outside 1..100")
+    return qtab
+
+
+def jpeg_write_bound(info):
+    """``cft_jpeg_write_bound``: a byte count no file laid out as ``info`` exceeds.  Needs no GPU."""
+    bound = ctypes.c_long(0)
+    if _lib.load().cft_jpeg_write_bound(info.ctypes.data, ctypes.byref(bound)) != OK:
+        raise ValueError("jpeg_write_bound: info was not made by jpeg_layout")
+    return bound.value
+
+
+def jpeg_write(coef, qtab, info):
+    """``cft_jpeg_write``: the bytes of the file whose quantised coefficients are ``coef`` (contiguous int16, ``info["ncoef"]`` values, the
+    layout of ``jpeg_entropy``).  Needs no GPU; callable from many threads at once (the call releases the GIL)."""
+    lib = _lib.load()
+    if coef.dtype != np.int16 or coef.size != int(info["ncoef"]) or not coef.flags.c_contiguous:
+        raise ValueError(f"jpeg_write: coef must be a contiguous int16 array of {int(info['ncoef'])} values")
+    if qtab.dtype != np.uint16 or qtab.size != QTAB_BYTES // 2 or not qtab.flags.c_contiguous:
+        raise ValueError(f"jpeg_write: qtab must be a contiguous uint16 array of {QTAB_BYTES // 2} values")
+    cap = jpeg_write_bound(info)
+    out = np.empty(cap, dtype=np.uint8)
+    n = ctypes.c_long(0)
+    st = lib.cft_jpeg_write(coef.ctypes.data, qtab.ctypes.data, info.ctypes.data, out.ctypes.data, cap, ctypes.byref(n))
+    if st != OK:
+        raise ValueError(f"jpeg_write: status {st} ({'a coefficient outside the baseline range' if st == UNSUPPORTED else 'bad tables or info'})")
+    return out[:n.value].tobytes()
+
+
+def jpeg_encode_coef(table_dev, table_host, n):
+    """Launch ``cft_jpeg_encode_coef`` on the current stream: ``table_dev`` / ``table_host`` uint8 tensors holding the same ``n``
+    JPEG_ENC_DESC rows on the device and on the host."""
+    if not table_dev.is_cuda or table_host.is_cuda:
+        raise RuntimeError("jpeg_encode_coef: table_dev lives on the device, table_host on the host (this package runs on MI355X only)")
+    for t in (table_dev, table_host):
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < n * JPEG_ENC_DESC.itemsize:
+            raise ValueError(f"jpeg_encode_coef: a table is a contiguous uint8 tensor of at least {n} x {JPEG_ENC_DESC.itemsize} bytes")
+    st = _lib.load().cft_jpeg_encode_coef(table_dev.data_ptr(), table_host.data_ptr(), n, torch.cuda.current_stream(table_dev.device).cuda_stream)
+    _lib.check(st, "cft_jpeg_encode_coef")
+
+
+class EncodeJob:
+    """What ``encode_jpeg_start`` leaves behind: the coefficients of every image on their way into pinned memory.  ``file_bytes(k)``
+    waits for the copy (an event, not the device) and codes image ``k`` on the calling thread - any thread, several at once."""
+
+    def __init__(self, infos, offsets, qtab, pinned, event, keep):
+        self.infos, self.offsets, self.qtab, self.pinned, self.event = infos, offsets, qtab, pinned, event
+        self._keep = keep                                  # the sources and device buffers stay alive until the copy is done
+        self._host = pinned.numpy()
+
+    def __len__(self):
+        return len(self.infos)
+
+    def wait(self):
+        self.event.synchronize()
+        self._keep = None
+
+    def coefficients(self, k):
+        """The int16 coefficients of image ``k`` (a view of the pinned buffer) once the copy has arrived."""
+        self.event.synchronize()
+        return self._host[self.offsets[k]:self.offsets[k] + int(self.infos[k]["ncoef"])]
+
+    def file_bytes(self, k):
+        return jpeg_write(self.coefficients(k), self.qtab, self.infos[k])
+
+    def all_bytes(self, pool=None):
+        if pool is not None:
+            out = list(pool.map(self.file_bytes, range(len(self))))
+        elif len(self) == 1:
+            out = [self.file_bytes(0)]
+        else:
+            with ThreadPoolExecutor(min(MAX_ENCODE_THREADS, len(self))) as own:
+                out = list(own.map(self.file_bytes, range(len(self))))
+        self._keep = None
+        return out
+
+
+def encode_jpeg_start(images, quality=75, subsampling="4:2:0"):
+    """The device stage of ``encode_jpeg_batch``: ``images`` are uint8 CUDA tensors of one device, [h, w, 3] RGB or grey ([h, w] or
+    [h, w, 1]), of mixed sizes; a view whose rows are strided (padded rows, a crop) is read in place, anything else is made contiguous.
+    One pinned buffer with the tables and the descriptor rows, one upload, one ``cft_jpeg_encode_coef`` launch and one non-blocking copy
+    of all coefficients into pinned memory on the current stream, then an event.  Nothing here waits for the device.  Returns an
+    ``EncodeJob``."""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"encode_jpeg: subsampling {subsampling!r} is not one of '4:4:4', '4:2:2', '4:2:0' (or PIL's 0, 1, 2)")
+    if not len(images):
+        raise ValueError("encode_jpeg: no images")
+    qtab = jpeg_quality_tables(quality)
+    device = images[0].device
+    srcs, infos, offsets, total = [], [], [], 0
+    for k, im in enumerate(images):
+        if not torch.is_tensor(im) or not im.is_cuda or im.dtype != torch.uint8 or im.device != device or im.dim() not in (2, 3) or \
+                (im.dim() == 3 and im.shape[2] not in (1, 3)):
+            raise ValueError(f"encode_jpeg: images[{k}] must be a uint8 CUDA tensor [h, w, 3], [h, w, 1] or [h, w] on {device}")
+        if im.dim() == 2:
+            im = im.unsqueeze(2)
+        h, w, nc = im.shape
+        if im.stride(2) != 1 or im.stride(1) != nc or (h > 1 and im.stride(0) < nc * w):
+            im = im.contiguous()
+        hmax, vmax = SUBSAMPLING[subsampling] if nc == 3 else (1, 1)
+        info = jpeg_layout(w, h, nc, hmax, vmax)
+        srcs.append(im)
+        infos.append(info)
+        offsets.append(total)
+        total += int(info["ncoef"])                        # a multiple of 64 values: every image starts on a 128-byte boundary
+    n = len(srcs)
+    head = QTAB_BYTES + n * JPEG_ENC_DESC.itemsize
+    staging = torch.empty(head, dtype=torch.uint8).pin_memory()
+    host = staging.numpy()
+    host[:QTAB_BYTES].view(np.uint16)[:] = qtab.reshape(-1)
+    table = host[QTAB_BYTES:].view(JPEG_ENC_DESC)
+    with torch.cuda.device(device):
+        staged = torch.empty(head, dtype=torch.uint8, device=device)
+        coef = torch.empty(total, dtype=torch.int16, device=device)
+        for row, im, info, off in zip(table, srcs, infos, offsets):
+            h, w, nc = im.shape
+            row["src"], row["qtab"], row["qtab_host"], row["coef"] = im.data_ptr(), staged.data_ptr(), staging.data_ptr(), coef.data_ptr() + 2 * off
+            row["src_stride"] = im.stride(0) if h > 1 else max(im.stride(0), nc * w)
+            for key in ("width", "height", "ncomp", "hmax", "vmax", "bw", "bh"):
+                row[key] = info[key]
+            row["reserved"] = 0
+        staged.copy_(staging, non_blocking=True)
+        jpeg_encode_coef(staged[QTAB_BYTES:], staging[QTAB_BYTES:], n)
+        pinned = torch.empty(total, dtype=torch.int16).pin_memory()
+        pinned.copy_(coef, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+    return EncodeJob(infos, offsets, qtab, pinned, event, (srcs, staged, staging, coef))
+
+
+def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", pool=None):
+    """The bytes of ``Image.fromarray(a).save(f, 'JPEG', quality=quality, subsampling=subsampling)`` for every image of ``images``
+    (``encode_jpeg_start``), byte for byte: a list of ``bytes``.  ``pool``: an executor for the host coding (default: up to 16 threads
+    of its own).  ``Image.save`` without options is quality 75 at 4:2:0."""
+    return encode_jpeg_start(images, quality, subsampling).all_bytes(pool)
+
+
+def is_jpeg_name(path):
+    return str(path).lower().endswith(JPEG_SUFFIXES)

@@ -17,6 +17,7 @@ import torch
 from .. import _lib
 from .. import ops
 from ..ops import _require_cuda, detect_render
+from .jpeg import encode_jpeg_start, is_jpeg_name
 
 RENDER_LABELS, RENDER_CONF = _lib._consts["CFT_RENDER_LABELS"], _lib._consts["CFT_RENDER_CONF"]
 RENDER_CONF1, RENDER_SIGNED = _lib._consts["CFT_RENDER_CONF1"], _lib._consts["CFT_RENDER_SIGNED"]
@@ -326,7 +327,7 @@ def save_mosaic(array, fname):
     Image.fromarray(array).save(fname)          # :202
 
 
-def plot_images(images, targets, paths=None, fname='images.jpg', names=None, max_size=640, max_subplots=16):
+def plot_images(images, targets, paths=None, fname='images.jpg', names=None, max_size=640, max_subplots=16, device_jpeg=False):
     """The reference's ``plot_images`` (utils/plots.py:128-203) on the GPU: the first ``max_subplots`` images of a batch in a square
     grid (column-major, as there), the targets drawn in, file names and cell borders on top, reduced to at most 1280 pixels a side and
     saved when ``fname`` is given.
@@ -343,6 +344,8 @@ def plot_images(images, targets, paths=None, fname='images.jpg', names=None, max
 
     Everything stays on the device and nothing synchronises until the bytes are needed: saving is one device-to-host copy per mosaic
     and a PIL save, and there the kernel's flag word is read: a class outside the table or more drawn targets than slots raise ValueError.
+    ``device_jpeg`` with a .jpg / .jpeg name: the file is written by ``utils.jpeg.encode_jpeg_start`` instead (the DCT on the device, the
+    quantised coefficients copied, Huffman coding on the host) and holds the same bytes.
 
     The raster is this project's own (cv2 is absent: "parity unpinned"), defined in include/cft_hip.h: float32 bilinear resize in
     OpenCV's published coordinate convention, the hard-edged boxes and atlas text of ``plot_one_box``, ``' d.d'`` confidences.
@@ -350,7 +353,14 @@ def plot_images(images, targets, paths=None, fname='images.jpg', names=None, max
     spill into the neighbouring cell); coordinates are truncated relative to the cell; the file name is drawn with its top-left at
     (block_x + 5, block_y + 5)."""
     mosaics, flag, _ = plot_images_device(images, targets, paths, names, max_size, max_subplots, reduce=bool(fname))
-    if fname:
+    if fname and device_jpeg and is_jpeg_name(fname):
+        job = encode_jpeg_start(list(mosaics))
+        if flag is not None:
+            check_mosaic_flag(int(flag.item()))
+        for data, f in zip(job.all_bytes(), mosaic_file_names(fname, len(job))):
+            with open(f, 'wb') as fh:
+                fh.write(data)
+    elif fname:
         host = [m.cpu() for m in mosaics]
         if flag is not None:
             check_mosaic_flag(int(flag.item()))

@@ -3,7 +3,8 @@
     python tools/detect.py --weights W.pt --source1 RGB_DIR --source2 IR_DIR [--img-size 640] [--conf-thres 0.4] [--batch-size 8]
                            [--save-txt] [--save-conf] [--save-crop] [--nosave] [--hide-labels] [--line-thickness 2] ...
 
-The options and their defaults are the reference's (detect_twostream.py:198-221) plus ``--batch-size``.  Results go to
+The options and their defaults are the reference's (detect_twostream.py:198-221) plus ``--batch-size`` and ``--device-jpeg`` (saved
+.jpg / .jpeg images are encoded on the GPU instead of by PIL, to the same bytes; other suffixes stay on PIL).  Results go to
 ``--project/--name`` (incremented): ``<stem>_rgb.<ext>`` / ``<stem>_ir.<ext>`` with the boxes drawn, ``labels/<stem>.txt``,
 ``crops/<class>/<stem>.jpg``.  ``--view-img``, ``--update``, ``--augment`` and webcam / stream / video sources raise."""
 import os
@@ -17,7 +18,10 @@ from msod_amd.detect import detect, make_parser  # noqa: E402
 
 
 def main(argv=None):
-    opt = make_parser().parse_args(argv)
+    parser = make_parser()
+    parser.add_argument('--device-jpeg', action='store_true',
+                        help='encode saved .jpg / .jpeg images on the GPU (colour, DCT, quantisation; Huffman coding on host threads): the bytes PIL writes')
+    opt = parser.parse_args(argv)
     print(opt)
     with torch.no_grad():
         return detect(opt=opt)

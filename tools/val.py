@@ -35,6 +35,7 @@ def main(argv=None):
     ap.add_argument("--save-txt", action="store_true")
     ap.add_argument("--save-json", action="store_true")
     ap.add_argument("--plots", action="store_true", help="test_batch{0,1,2}_{labels,pred}[_ir].jpg of the first three batches in --save-dir")
+    ap.add_argument("--device-jpeg", action="store_true", help="encode the --plots mosaics on the GPU instead of with PIL (the same bytes)")
     ap.add_argument("--save-dir", default="runs/val")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--verbose", action="store_true")
@@ -73,7 +74,7 @@ def main(argv=None):
     details = {}
     evaluate(model, loader, nc, conf_thres=opt.conf_thres, iou_thres=opt.iou_thres, single_cls=opt.single_cls, save_txt=opt.save_txt,
              save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json or opt.plots) else None, details=details,
-             plots=opt.plots, names=names if opt.plots else None)
+             plots=opt.plots, names=names if opt.plots else None, device_jpeg=opt.device_jpeg)
     res = details["result"]
 
     print(('%20s' + '%12s' * 7) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.75', 'mAP@.5:.95'))
