@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip", "jpeg_encode.hip")
 
 HEADER = os.path.join(_HERE, "..", "include", "cft_hip.h")
-HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "resize_common.h", "conv_gemm_asm.inc")
+HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "resize_common.h", "jpeg_common.h", "conv_gemm_asm.inc")
 
 _SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong}
 _RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}

@@ -1,4 +1,6 @@
-// Baseline JPEG decoding in two halves (include/cft_hip.h, where the subset and the arithmetic are defined).
+// Baseline JPEG decoding in two halves (include/cft_hip.h, where the subset and the arithmetic are defined).  What the decoder shares
+// with the encoder (jpeg_encode.hip) is in jpeg_common.h: the geometry of a file, the coefficient layout, the geometry guard of a table
+// row, the zigzag order, the DCT constants and the workgroup shape of the DCT kernels.
 //
 // Host half (cft_jpeg_info, cft_jpeg_entropy): marker parsing and Huffman decoding, plain C++ without a HIP call.  It is re-entrant: the
 // parse state lives on the caller's stack, nothing is allocated, no global is written (not even cft_last_error's text), so a pool of
@@ -8,20 +10,15 @@
 //
 // Device half (cft_jpeg_decode_u8): two launches for a whole batch, grid (work of the largest image, image).
 //   jpeg_idct_kernel   8 lanes per 8x8 block, 32 blocks per workgroup: a lane dequantises and transforms one column, the block is
-//                      transposed through LDS (72-dword block stride: the 64 lanes of a wave hit 64 different banks on the column
-//                      writes, and a lane reads its row back as two 16-byte words), the lane transforms one row and stores its 8
-//                      bytes as one 8-byte word into the component's plane.
+//                      transposed through LDS (JPEG_LDS_STRIDE), the lane transforms one row and stores its 8 bytes as one 8-byte
+//                      word into the component's plane.
 //   jpeg_colour_kernel one thread per 4 consecutive pixels of a row: luma as one dword, chroma through the h2v1 / h2v2 triangle taps
 //                      with every neighbour index clamped to the component's downsampled size, YCbCr -> RGB, 12 bytes out.
 // No atomics, no inline assembly; every plane byte and every output byte is written once by one thread.  All arithmetic is integer.
-#include "cft_common.h"
-#include <string.h>
+#include "jpeg_common.h"
 
 // ------------------------------------------------------------------------------------------------ host half
 namespace {
-
-const unsigned char JPG_ZIGZAG[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 #define JPG_LUT_BITS 9
 
@@ -73,7 +70,7 @@ int jpg_parse(const unsigned char* d, long n, JpgParse& P) {
   if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return CFT_JPEG_UNSUPPORTED;
   long pos = 2;
   bool sof = false, jfif = false, adobe = false;
-  int adobe_transform = -1, comp_id[3] = {0, 0, 0}, nc = 0;
+  int adobe_transform = -1, comp_id[3] = {0, 0, 0}, nc = 0, restart = 0;
   cft_jpeg_info_t& I = P.info;
   for (;;) {
     if (pos + 2 > n || d[pos] != 0xFF) return CFT_JPEG_UNSUPPORTED;
@@ -112,13 +109,13 @@ int jpg_parse(const unsigned char* d, long n, JpgParse& P) {
       while (sl > 0) {
         const int pq = seg[0] >> 4, t = seg[0] & 15;
         if (pq != 0 || t > 3 || sl < 65) return CFT_JPEG_UNSUPPORTED;
-        for (int i = 0; i < 64; ++i) P.q[t][JPG_ZIGZAG[i]] = seg[1 + i];
+        for (int i = 0; i < 64; ++i) P.q[t][JPEG_ZIGZAG[i]] = seg[1 + i];
         P.qdef[t] = true;
         seg += 65; sl -= 65;
       }
     } else if (m == 0xDD) {                                        // DRI
       if (sl != 2) return CFT_JPEG_UNSUPPORTED;
-      I.restart_interval = jpg_be16(seg);
+      restart = jpg_be16(seg);
     } else if (m == 0xE0) {
       if (sl >= 5 && memcmp(seg, "JFIF", 5) == 0) jfif = true;
     } else if (m == 0xEE) {
@@ -143,25 +140,12 @@ int jpg_parse(const unsigned char* d, long n, JpgParse& P) {
   // colour space: what libjpeg would convert from must be YCbCr (or one grey component)
   if (adobe && nc == 3 && adobe_transform != 1) return CFT_JPEG_UNSUPPORTED;
   if (nc == 3 && !jfif && !adobe && comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B') return CFT_JPEG_UNSUPPORTED;
-  // sampling
-  if (nc == 1) {
-    if (I.hs[0] != 1 || I.vs[0] != 1) return CFT_JPEG_UNSUPPORTED;
-  } else {
-    const bool luma_ok = (I.hs[0] == 1 && I.vs[0] == 1) || (I.hs[0] == 2 && I.vs[0] == 1) || (I.hs[0] == 2 && I.vs[0] == 2);
-    if (!luma_ok || I.hs[1] != 1 || I.vs[1] != 1 || I.hs[2] != 1 || I.vs[2] != 1) return CFT_JPEG_UNSUPPORTED;
-  }
-  I.hmax = I.hs[0]; I.vmax = I.vs[0];
-  I.mcus_x = (I.width + 8 * I.hmax - 1) / (8 * I.hmax);
-  I.mcus_y = (I.height + 8 * I.vmax - 1) / (8 * I.vmax);
-  long blocks = 0;
-  for (int c = 0; c < nc; ++c) {
-    I.bw[c] = I.mcus_x * I.hs[c]; I.bh[c] = I.mcus_y * I.vs[c];
-    I.cw[c] = (I.width * I.hs[c] + I.hmax - 1) / I.hmax; I.ch[c] = (I.height * I.vs[c] + I.vmax - 1) / I.vmax;
-    blocks += (long)I.bw[c] * I.bh[c];
-  }
+  // sampling: chroma 1x1 and a luma sampling of the subset; the rest of the info follows from these five numbers
+  for (int c = 1; c < nc; ++c)
+    if (I.hs[c] != 1 || I.vs[c] != 1) return CFT_JPEG_UNSUPPORTED;
+  if (!jpeg_geometry(I.width, I.height, nc, I.hs[0], I.vs[0], I)) return CFT_JPEG_UNSUPPORTED;
+  I.restart_interval = restart;
   if (nc == 3 && I.hmax == 2 && I.cw[1] <= 2 && !(I.cw[1] == 1 && (I.vmax == 1 || I.ch[1] == 1))) return CFT_JPEG_UNSUPPORTED;   // libjpeg replicates here
-  I.ncoef = 64 * blocks;
-  I.plane_bytes = 64 * blocks;
   return CFT_OK;
 }
 
@@ -176,8 +160,7 @@ struct JpgBits {
 inline void jpg_refill(JpgBits& b) {
   if (b.bits <= 32 && !b.marker && b.end - b.p >= 4) {
     const uint32_t w = ((uint32_t)b.p[0] << 24) | ((uint32_t)b.p[1] << 16) | ((uint32_t)b.p[2] << 8) | b.p[3];
-    const uint32_t x = ~w;                                         // a zero byte of x is a 0xFF byte of w
-    if (((x - 0x01010101u) & ~x & 0x80808080u) == 0) {
+    if (jpeg_no_ff(w)) {
       b.buf |= (uint64_t)w << (32 - b.bits);
       b.bits += 32; b.p += 4;
       return;
@@ -266,11 +249,10 @@ extern "C" int cft_jpeg_entropy(const unsigned char* bytes, long nbytes, short* 
   if (memcmp(&I, info, sizeof I) != 0) return CFT_EINVAL;           // the buffers were sized for another file
   memset(coef, 0, (size_t)I.ncoef * sizeof(short));
   memset(qtab, 0, CFT_JPEG_QTAB_BYTES);
-  long base[3] = {0, 0, 0};
-  for (int c = 0; c < I.ncomp; ++c) {
+  for (int c = 0; c < I.ncomp; ++c)
     for (int i = 0; i < 64; ++i) qtab[c * 64 + i] = P.q[P.tq[c]][i];
-    if (c) base[c] = base[c - 1] + 64L * I.bw[c - 1] * I.bh[c - 1];
-  }
+  long base[3];
+  jpeg_comp_bases(I, base);
   JpgBits b = {bytes + P.scan, bytes + nbytes, 0, 0, false};
   int pred[3] = {0, 0, 0};
   int left = I.restart_interval, rst = 0;
@@ -287,7 +269,7 @@ extern "C" int cft_jpeg_entropy(const unsigned char* bytes, long nbytes, short* 
         const uint16_t* q = P.q[P.tq[c]];
         for (int by = 0; by < I.vs[c]; ++by) {
           for (int bx = 0; bx < I.hs[c]; ++bx) {
-            short* blk = coef + base[c] + 64 * ((long)(my * I.vs[c] + by) * I.bw[c] + (mx * I.hs[c] + bx));
+            short* blk = jpeg_block_at(coef, I, base, c, my * I.vs[c] + by, mx * I.hs[c] + bx);
             int s = jpg_symbol(b, hd);
             if (s < 0 || s > 11) return CFT_JPEG_UNSUPPORTED;
             if (s) {
@@ -311,7 +293,7 @@ extern "C" int cft_jpeg_entropy(const unsigned char* bytes, long nbytes, short* 
               if (k > 63) return CFT_JPEG_UNSUPPORTED;
               int v;
               if (!jpg_receive(b, s, v)) return CFT_JPEG_UNSUPPORTED;
-              const int nat = JPG_ZIGZAG[k];
+              const int nat = JPEG_ZIGZAG[k];
               if (!jpg_fits(v, q[nat])) return CFT_JPEG_UNSUPPORTED;
               blk[nat] = (short)v;
             }
@@ -326,25 +308,21 @@ extern "C" int cft_jpeg_entropy(const unsigned char* bytes, long nbytes, short* 
 }
 
 // ------------------------------------------------------------------------------------------------ device half
-#define JPG_THREADS 256
-#define JPG_WG_BLOCKS (JPG_THREADS / 8)
-#define JPG_LDS_STRIDE 72              // dwords per block in LDS: 64 + 8, see the head of the file
-
 // jpeg_idct_islow's one-dimensional butterfly on v[0..7], in place, results descaled by `shift`.  Even part, odd part, recombination:
 // the published order of operations.  In the first pass tmp0 / tmp1 carry CONST_BITS, as every product does.
 __device__ __forceinline__ void jpg_idct_1d(int v[8], const int shift) {
-  int z1 = (v[2] + v[6]) * 4433;
-  const int e2 = z1 + v[6] * -15137;
-  const int e3 = z1 + v[2] * 6270;
+  int z1 = (v[2] + v[6]) * FIX_0_541196100;
+  const int e2 = z1 + v[6] * -FIX_1_847759065;
+  const int e3 = z1 + v[2] * FIX_0_765366865;
   const int e0 = (v[0] + v[4]) << 13;
   const int e1 = (v[0] - v[4]) << 13;
   const int t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
   int t0 = v[7], t1 = v[5], t2 = v[3], t3 = v[1];
   z1 = t0 + t3;
   int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-  const int z5 = (z3 + z4) * 9633;
-  t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
-  z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
+  const int z5 = (z3 + z4) * FIX_1_175875602;
+  t0 *= FIX_0_298631336; t1 *= FIX_2_053119869; t2 *= FIX_3_072711026; t3 *= FIX_1_501321110;
+  z1 *= -FIX_0_899976223; z2 *= -FIX_2_562915447; z3 *= -FIX_1_961570560; z4 *= -FIX_0_390180644;
   z3 += z5; z4 += z5;
   t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
   const int r = 1 << (shift - 1);
@@ -354,25 +332,17 @@ __device__ __forceinline__ void jpg_idct_1d(int v[8], const int shift) {
   v[3] = (t13 + t0 + r) >> shift; v[4] = (t13 - t0 + r) >> shift;
 }
 
-__device__ __forceinline__ int jpg_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ __forceinline__ int jpg_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-__global__ void __launch_bounds__(JPG_THREADS) jpeg_idct_kernel(const cft_jpeg_desc_t* __restrict__ table, unsigned char* __restrict__ ws) {
-  __shared__ __attribute__((aligned(16))) int tile[JPG_WG_BLOCKS * JPG_LDS_STRIDE];
+__global__ void __launch_bounds__(JPEG_THREADS) jpeg_idct_kernel(const cft_jpeg_desc_t* __restrict__ table, unsigned char* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) int tile[JPEG_WG_BLOCKS * JPEG_LDS_STRIDE];
   const cft_jpeg_desc_t& d = table[blockIdx.y];                    // uniform over the workgroup
-  const int nb0 = d.bw[0] * d.bh[0], nb1 = d.ncomp == 3 ? d.bw[1] * d.bh[1] : 0, nb2 = d.ncomp == 3 ? d.bw[2] * d.bh[2] : 0;
-  const long total = (long)nb0 + nb1 + nb2;
-  const int local = threadIdx.x >> 3, lane = threadIdx.x & 7;
-  const long blk = (long)blockIdx.x * JPG_WG_BLOCKS + local;
-  const bool active = blk < total;
-  int c = 0;
-  long rel = blk, before = 0;
-  if (active && rel >= nb0) {
-    rel -= nb0; before = nb0; c = 1;
-    if (rel >= nb1) { rel -= nb1; before += nb1; c = 2; }
-  }
+  const JpegBlock b = jpeg_locate(d);
+  const int c = b.c, local = b.local, lane = b.lane;
+  const long blk = b.blk, rel = b.rel, before = b.before;
+  const bool active = b.active;
   int v[8];
-  int* t = tile + local * JPG_LDS_STRIDE;
+  int* t = tile + local * JPEG_LDS_STRIDE;
   if (active) {
     const short* src = d.coef + blk * 64 + lane;
     const unsigned short* q = d.qtab + c * 64 + lane;
@@ -388,19 +358,19 @@ __global__ void __launch_bounds__(JPG_THREADS) jpeg_idct_kernel(const cft_jpeg_d
   for (int j = 0; j < 8; ++j) v[j] = t[lane * 8 + j];
   jpg_idct_1d(v, 18);                                              // row `lane`
   uint2 out;
-  out.x = (unsigned)jpg_u8(v[0] + 128) | ((unsigned)jpg_u8(v[1] + 128) << 8) | ((unsigned)jpg_u8(v[2] + 128) << 16) | ((unsigned)jpg_u8(v[3] + 128) << 24);
-  out.y = (unsigned)jpg_u8(v[4] + 128) | ((unsigned)jpg_u8(v[5] + 128) << 8) | ((unsigned)jpg_u8(v[6] + 128) << 16) | ((unsigned)jpg_u8(v[7] + 128) << 24);
+  out.x = (unsigned)jpeg_u8(v[0] + 128) | ((unsigned)jpeg_u8(v[1] + 128) << 8) | ((unsigned)jpeg_u8(v[2] + 128) << 16) | ((unsigned)jpeg_u8(v[3] + 128) << 24);
+  out.y = (unsigned)jpeg_u8(v[4] + 128) | ((unsigned)jpeg_u8(v[5] + 128) << 8) | ((unsigned)jpeg_u8(v[6] + 128) << 16) | ((unsigned)jpeg_u8(v[7] + 128) << 24);
   const int bw = d.bw[c];
   const long by = rel / bw, bx = rel % bw;
   unsigned char* dst = ws + d.plane_off + 64 * before + (by * 8 + lane) * (8L * bw) + bx * 8;
   *reinterpret_cast<uint2*>(dst) = out;
 }
 
-__global__ void __launch_bounds__(JPG_THREADS) jpeg_colour_kernel(const cft_jpeg_desc_t* __restrict__ table, const unsigned char* __restrict__ ws) {
+__global__ void __launch_bounds__(JPEG_THREADS) jpeg_colour_kernel(const cft_jpeg_desc_t* __restrict__ table, const unsigned char* __restrict__ ws) {
   const cft_jpeg_desc_t& d = table[blockIdx.y];
   const int W = d.width, H = d.height;
   const int gpr = (W + 3) >> 2;                                    // 4-pixel groups per row
-  const long g = (long)blockIdx.x * JPG_THREADS + threadIdx.x;
+  const long g = (long)blockIdx.x * JPEG_THREADS + threadIdx.x;
   if (g >= (long)gpr * H) return;
   const int y = (int)(g / gpr), x0 = (int)(g % gpr) * 4;
   const unsigned char* p0 = ws + d.plane_off;
@@ -447,9 +417,9 @@ __global__ void __launch_bounds__(JPG_THREADS) jpeg_colour_kernel(const cft_jpeg
     int rgb[3] = {Y, Y, Y};
     if (d.ncomp == 3) {
       const int u = cb[j] - 128, w = cr[j] - 128;
-      rgb[0] = jpg_u8(Y + ((91881 * w + 32768) >> 16));
-      rgb[1] = jpg_u8(Y + ((-22554 * u - 46802 * w + 32768) >> 16));
-      rgb[2] = jpg_u8(Y + ((116130 * u + 32768) >> 16));
+      rgb[0] = jpeg_u8(Y + ((91881 * w + 32768) >> 16));
+      rgb[1] = jpeg_u8(Y + ((-22554 * u - 46802 * w + 32768) >> 16));
+      rgb[2] = jpeg_u8(Y + ((116130 * u + 32768) >> 16));
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) o[(3 * j + k) >> 2] |= (unsigned)rgb[k] << (8 * ((3 * j + k) & 3));
@@ -478,19 +448,8 @@ extern "C" int cft_jpeg_decode_u8(const void* table_dev, const void* table_host,
     const cft_jpeg_desc_t& d = rows[i];
     CFT_REQUIRE(d.coef && d.qtab && d.dst, "cft_jpeg_decode_u8: null pointer in the table");
     CFT_REQUIRE(((uintptr_t)d.coef & 1) == 0 && ((uintptr_t)d.qtab & 1) == 0, "cft_jpeg_decode_u8: misaligned coefficients or tables");
-    CFT_REQUIRE(d.width >= 1 && d.height >= 1 && d.width <= CFT_JPEG_MAX_SIDE && d.height <= CFT_JPEG_MAX_SIDE, "cft_jpeg_decode_u8: image size out of range");
-    CFT_REQUIRE(d.ncomp == 1 || d.ncomp == 3, "cft_jpeg_decode_u8: 1 or 3 components");
-    if (d.ncomp == 1)
-      CFT_REQUIRE(d.hmax == 1 && d.vmax == 1, "cft_jpeg_decode_u8: one component is sampled 1x1");
-    else
-      CFT_REQUIRE((d.hmax == 1 && d.vmax == 1) || (d.hmax == 2 && d.vmax == 1) || (d.hmax == 2 && d.vmax == 2), "cft_jpeg_decode_u8: luma sampling outside 1x1, 2x1, 2x2");
-    const int mx = (d.width + 8 * d.hmax - 1) / (8 * d.hmax), my = (d.height + 8 * d.vmax - 1) / (8 * d.vmax);
-    long blocks = 0;
-    for (int c = 0; c < 3; ++c) {
-      const int bw = c >= d.ncomp ? 0 : (c ? mx : mx * d.hmax), bh = c >= d.ncomp ? 0 : (c ? my : my * d.vmax);
-      CFT_REQUIRE(d.bw[c] == bw && d.bh[c] == bh, "cft_jpeg_decode_u8: block grid does not belong to this size and sampling");
-      blocks += (long)bw * bh;
-    }
+    long blocks;
+    JPEG_REQUIRE_GEOMETRY("cft_jpeg_decode_u8", d, blocks);
     CFT_REQUIRE(d.dst_stride >= 3L * d.width, "cft_jpeg_decode_u8: bad destination row stride");
     CFT_REQUIRE(d.plane_off >= 0 && (d.plane_off & 15) == 0, "cft_jpeg_decode_u8: plane offset negative or not a multiple of 16");
     CFT_REQUIRE(d.plane_off >= prev_end, "cft_jpeg_decode_u8: plane ranges overlap or do not ascend");
@@ -501,11 +460,11 @@ extern "C" int cft_jpeg_decode_u8(const void* table_dev, const void* table_host,
     max_groups = groups > max_groups ? groups : max_groups;
   }
   const cft_jpeg_desc_t* dev = static_cast<const cft_jpeg_desc_t*>(table_dev);
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + JPG_WG_BLOCKS - 1) / JPG_WG_BLOCKS), n), dim3(JPG_THREADS), 0, as_stream(stream),
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + JPEG_WG_BLOCKS - 1) / JPEG_WG_BLOCKS), n), dim3(JPEG_THREADS), 0, as_stream(stream),
                      dev, static_cast<unsigned char*>(workspace));
   int st = cft_check_launch("jpeg_idct_kernel");
   if (st != CFT_OK) return st;
-  hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_groups + JPG_THREADS - 1) / JPG_THREADS), n), dim3(JPG_THREADS), 0, as_stream(stream),
+  hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_groups + JPEG_THREADS - 1) / JPEG_THREADS), n), dim3(JPEG_THREADS), 0, as_stream(stream),
                      dev, static_cast<const unsigned char*>(workspace));
   return cft_check_launch("jpeg_colour_kernel");
 }

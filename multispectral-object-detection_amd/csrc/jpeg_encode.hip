@@ -1,4 +1,5 @@
-// Baseline JPEG encoding in two halves, the decoder's (jpeg.hip) in the other direction; include/cft_hip.h defines the arithmetic.
+// Baseline JPEG encoding in two halves, the decoder's (jpeg.hip) in the other direction; include/cft_hip.h defines the arithmetic, and
+// jpeg_common.h holds what the two share (geometry, coefficient layout, row guard, zigzag order, DCT constants, workgroup shape).
 //
 // Host half (cft_jpeg_layout, cft_jpeg_quality_tables, cft_jpeg_write_bound, cft_jpeg_write): geometry, tables, headers and Huffman
 // coding, plain C++ without a HIP call.  Re-entrant: the code tables are built on the caller's stack, nothing is allocated, no global
@@ -8,17 +9,13 @@
 // Device half (cft_jpeg_encode_coef): one launch for a whole batch, grid (work of the largest image, image).
 //   jpeg_fdct_kernel   8 lanes per 8x8 block, 32 blocks per workgroup: a lane gathers one row of its block from the source (colour
 //                      conversion and the h2v1 / h2v2 box filter on the way, every index clamped), transforms it, the block is transposed
-//                      through LDS (72-dword block stride), the lane transforms and quantises one column, a second transpose gives it the
+//                      through LDS (JPEG_LDS_STRIDE), the lane transforms and quantises one column, a second transpose gives it the
 //                      8 coefficients of one row, stored as one 16-byte word.
 // No atomics, no inline assembly, no plane workspace; every coefficient is written once by one thread.  All arithmetic is integer.
-#include "cft_common.h"
-#include <string.h>
+#include "jpeg_common.h"
 
 // ------------------------------------------------------------------------------------------------ host half
 namespace {
-
-const unsigned char ENC_ZIGZAG[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ITU T.81 Annex K: table K.1 (luminance), K.2 (chrominance), natural order
 const unsigned char ENC_BASE_Q[2][64] = {
@@ -61,33 +58,10 @@ void enc_make_code(EncCode& c, const unsigned char* counts, const unsigned char*
   }
 }
 
-bool enc_sampling_ok(int ncomp, int hmax, int vmax) {
-  if (ncomp == 1) return hmax == 1 && vmax == 1;
-  return ncomp == 3 && ((hmax == 1 && vmax == 1) || (hmax == 2 && vmax == 1) || (hmax == 2 && vmax == 2));
-}
-
-bool enc_layout(int width, int height, int ncomp, int hmax, int vmax, cft_jpeg_info_t& I) {
-  if (width < 1 || height < 1 || width > CFT_JPEG_MAX_SIDE || height > CFT_JPEG_MAX_SIDE || !enc_sampling_ok(ncomp, hmax, vmax)) return false;
-  memset(&I, 0, sizeof I);
-  I.width = width; I.height = height; I.ncomp = ncomp; I.hmax = hmax; I.vmax = vmax;
-  I.mcus_x = (width + 8 * hmax - 1) / (8 * hmax);
-  I.mcus_y = (height + 8 * vmax - 1) / (8 * vmax);
-  long blocks = 0;
-  for (int c = 0; c < ncomp; ++c) {
-    I.hs[c] = c ? 1 : hmax; I.vs[c] = c ? 1 : vmax;
-    I.bw[c] = I.mcus_x * I.hs[c]; I.bh[c] = I.mcus_y * I.vs[c];
-    I.cw[c] = (width * I.hs[c] + hmax - 1) / hmax; I.ch[c] = (height * I.vs[c] + vmax - 1) / vmax;
-    blocks += (long)I.bw[c] * I.bh[c];
-  }
-  I.ncoef = 64 * blocks;
-  I.plane_bytes = 64 * blocks;
-  return true;
-}
-
-// true when `info` is what enc_layout gives for its own first five fields
+// true when `info` is what jpeg_geometry gives for its own first five fields
 bool enc_info_ok(const cft_jpeg_info_t* info) {
   cft_jpeg_info_t I;
-  return enc_layout(info->width, info->height, info->ncomp, info->hmax, info->vmax, I) && memcmp(&I, info, sizeof I) == 0;
+  return jpeg_geometry(info->width, info->height, info->ncomp, info->hmax, info->vmax, I) && memcmp(&I, info, sizeof I) == 0;
 }
 
 long enc_header_bytes(int ncomp) {
@@ -118,8 +92,7 @@ inline void enc_put(EncOut& o, unsigned v, int n) {
   if (o.bits < 32) return;
   const int rest = o.bits - 32;
   const uint32_t w = (uint32_t)(o.acc >> rest);
-  const uint32_t x = ~w;                                           // a zero byte of x is a 0xFF byte of w
-  if (((x - 0x01010101u) & ~x & 0x80808080u) == 0 && o.end - o.p >= 4) {
+  if (jpeg_no_ff(w) && o.end - o.p >= 4) {
     o.p[0] = (unsigned char)(w >> 24); o.p[1] = (unsigned char)(w >> 16); o.p[2] = (unsigned char)(w >> 8); o.p[3] = (unsigned char)w;
     o.p += 4;
   } else {
@@ -165,7 +138,7 @@ inline void enc_segment(EncOut& o, int marker, const unsigned char* body, int n)
 extern "C" int cft_jpeg_layout(int width, int height, int ncomp, int hmax, int vmax, cft_jpeg_info_t* info) {
   if (!info) return CFT_EINVAL;
   cft_jpeg_info_t I;
-  if (!enc_layout(width, height, ncomp, hmax, vmax, I)) return CFT_EINVAL;
+  if (!jpeg_geometry(width, height, ncomp, hmax, vmax, I)) return CFT_EINVAL;
   *info = I;
   return CFT_OK;
 }
@@ -206,7 +179,7 @@ extern "C" int cft_jpeg_write(const short* coef, const unsigned short* qtab, con
   const int tables = I.ncomp == 3 ? 2 : 1;
   for (int t = 0; t < tables; ++t) {
     seg[0] = (unsigned char)t;
-    for (int i = 0; i < 64; ++i) seg[1 + i] = (unsigned char)qtab[t * 64 + ENC_ZIGZAG[i]];
+    for (int i = 0; i < 64; ++i) seg[1 + i] = (unsigned char)qtab[t * 64 + JPEG_ZIGZAG[i]];
     enc_segment(o, 0xDB, seg, 65);
   }
   seg[0] = 8;
@@ -236,12 +209,10 @@ extern "C" int cft_jpeg_write(const short* coef, const unsigned short* qtab, con
   enc_segment(o, 0xDA, seg, 4 + 2 * I.ncomp);
   if (o.full) return CFT_JPEG_SHORT_BUFFER;
 
-  long base[3] = {0, 0, 0};
+  long base[3];
+  jpeg_comp_bases(I, base);
   int real_bw[3], real_bh[3];
-  for (int c = 0; c < I.ncomp; ++c) {
-    if (c) base[c] = base[c - 1] + 64L * I.bw[c - 1] * I.bh[c - 1];
-    real_bw[c] = (I.cw[c] + 7) / 8; real_bh[c] = (I.ch[c] + 7) / 8;
-  }
+  for (int c = 0; c < 3; ++c) { real_bw[c] = (I.cw[c] + 7) / 8; real_bh[c] = (I.ch[c] + 7) / 8; }   // 0 for an absent component
   int pred[3] = {0, 0, 0};
   for (int my = 0; my < I.mcus_y; ++my) {
     for (int mx = 0; mx < I.mcus_x; ++mx) {
@@ -256,7 +227,7 @@ extern "C" int cft_jpeg_write(const short* coef, const unsigned short* qtab, con
               enc_put(o, ha.code[0], ha.len[0]);
               continue;
             }
-            const short* blk = coef + base[c] + 64 * ((long)gy * I.bw[c] + gx);
+            const short* blk = jpeg_block_at(coef, I, base, c, gy, gx);
             const int diff = (int)blk[0] - pred[c];
             pred[c] = blk[0];
             int s = enc_category(diff);
@@ -265,7 +236,7 @@ extern "C" int cft_jpeg_write(const short* coef, const unsigned short* qtab, con
             if (s) enc_put(o, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
             uint64_t nz = 0;                                          // bit k: the k-th coefficient in zigzag order is not zero
 #pragma unroll
-            for (int k = 1; k < 64; ++k) nz |= (uint64_t)(blk[ENC_ZIGZAG[k]] != 0) << k;
+            for (int k = 1; k < 64; ++k) nz |= (uint64_t)(blk[JPEG_ZIGZAG[k]] != 0) << k;
             int prev = 0;
             while (nz) {
               const int k = __builtin_ctzll(nz);
@@ -273,7 +244,7 @@ extern "C" int cft_jpeg_write(const short* coef, const unsigned short* qtab, con
               int run = k - prev - 1;
               prev = k;
               while (run > 15) { enc_put(o, ha.code[0xF0], ha.len[0xF0]); run -= 16; }
-              const int v = blk[ENC_ZIGZAG[k]];
+              const int v = blk[JPEG_ZIGZAG[k]];
               s = enc_category(v);
               if (s > 10) return CFT_JPEG_UNSUPPORTED;
               const int rs = (run << 4) | s;
@@ -294,10 +265,6 @@ extern "C" int cft_jpeg_write(const short* coef, const unsigned short* qtab, con
 }
 
 // ------------------------------------------------------------------------------------------------ device half
-#define ENC_THREADS 256
-#define ENC_WG_BLOCKS (ENC_THREADS / 8)
-#define ENC_LDS_STRIDE 72              // dwords per block in LDS: 64 + 8, as in jpeg.hip
-
 #define ENC_DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 
 // jpeg_fdct_islow's one-dimensional butterfly on v[0..7], in place: the row pass (PASS1) scales up by PASS1_BITS, the column pass
@@ -310,15 +277,15 @@ __device__ __forceinline__ void enc_fdct_1d(int v[8]) {
   constexpr int N = PASS1 ? 11 : 15;
   if (PASS1) { v[0] = (t10 + t11) * 4; v[4] = (t10 - t11) * 4; }
   else       { v[0] = ENC_DESCALE(t10 + t11, 2); v[4] = ENC_DESCALE(t10 - t11, 2); }
-  int z1 = (t12 + t13) * 4433;
-  v[2] = ENC_DESCALE(z1 + t13 * 6270, N);
-  v[6] = ENC_DESCALE(z1 - t12 * 15137, N);
+  int z1 = (t12 + t13) * FIX_0_541196100;
+  v[2] = ENC_DESCALE(z1 + t13 * FIX_0_765366865, N);
+  v[6] = ENC_DESCALE(z1 - t12 * FIX_1_847759065, N);
   z1 = t4 + t7;
   int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-  const int z5 = (z3 + z4) * 9633;
-  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
-  z1 *= -7373; z2 *= -20995;
-  z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+  const int z5 = (z3 + z4) * FIX_1_175875602;
+  const int a4 = t4 * FIX_0_298631336, a5 = t5 * FIX_2_053119869, a6 = t6 * FIX_3_072711026, a7 = t7 * FIX_1_501321110;
+  z1 *= -FIX_0_899976223; z2 *= -FIX_2_562915447;
+  z3 = z3 * -FIX_1_961570560 + z5; z4 = z4 * -FIX_0_390180644 + z5;
   v[7] = ENC_DESCALE(a4 + z1 + z3, N);
   v[5] = ENC_DESCALE(a5 + z2 + z4, N);
   v[3] = ENC_DESCALE(a6 + z2 + z3, N);
@@ -350,29 +317,22 @@ __device__ __forceinline__ void enc_row_rgb(const unsigned char* __restrict__ ro
   }
 }
 
-__global__ void __launch_bounds__(ENC_THREADS) jpeg_fdct_kernel(const cft_jpeg_enc_desc_t* __restrict__ table) {
-  __shared__ __attribute__((aligned(16))) int tile[2][ENC_WG_BLOCKS * ENC_LDS_STRIDE];
+__global__ void __launch_bounds__(JPEG_THREADS) jpeg_fdct_kernel(const cft_jpeg_enc_desc_t* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) int tile[2][JPEG_WG_BLOCKS * JPEG_LDS_STRIDE];
   const cft_jpeg_enc_desc_t& d = table[blockIdx.y];                // uniform over the workgroup
   const int W = d.width, H = d.height;
-  const int nb0 = d.bw[0] * d.bh[0], nb1 = d.ncomp == 3 ? d.bw[1] * d.bh[1] : 0, nb2 = d.ncomp == 3 ? d.bw[2] * d.bh[2] : 0;
-  const long total = (long)nb0 + nb1 + nb2;
-  const int local = threadIdx.x >> 3, lane = threadIdx.x & 7;
-  const long blk = (long)blockIdx.x * ENC_WG_BLOCKS + local;
-  const bool active = blk < total;
-  int c = 0;
-  long rel = blk;
-  if (active && rel >= nb0) {
-    rel -= nb0; c = 1;
-    if (rel >= nb1) { rel -= nb1; c = 2; }
-  }
+  const JpegBlock b = jpeg_locate(d);
+  const int c = b.c, local = b.local, lane = b.lane;
+  const long blk = b.blk, rel = b.rel;
+  const bool active = b.active;
   const int bw = active ? d.bw[c] : 1;
   const int by = (int)(rel / bw), bx = (int)(rel % bw);
   const int fx = c ? d.hmax : 1, fy = c ? d.vmax : 1;              // how much this component is downsampled
   const int cw = (W + fx - 1) / fx, ch = (H + fy - 1) / fy;
   const bool real = active && bx < (cw + 7) / 8 && by < (ch + 7) / 8;
   int v[8];
-  int* t0 = tile[0] + local * ENC_LDS_STRIDE;
-  int* t1 = tile[1] + local * ENC_LDS_STRIDE;
+  int* t0 = tile[0] + local * JPEG_LDS_STRIDE;
+  int* t1 = tile[1] + local * JPEG_LDS_STRIDE;
   if (real) {
     const int sy = min(by * 8 + lane, ch - 1);                     // rows past ch repeat the last downsampled row
     if (d.ncomp == 1) {
@@ -446,22 +406,14 @@ extern "C" int cft_jpeg_encode_coef(const void* table_dev, const void* table_hos
     CFT_REQUIRE(d.src && d.qtab && d.qtab_host && d.coef, "cft_jpeg_encode_coef: null pointer in the table");
     CFT_REQUIRE(((uintptr_t)d.qtab & 1) == 0 && ((uintptr_t)d.qtab_host & 1) == 0, "cft_jpeg_encode_coef: misaligned tables");
     CFT_REQUIRE(((uintptr_t)d.coef & 15) == 0, "cft_jpeg_encode_coef: coefficients not 16-byte aligned");
-    CFT_REQUIRE(d.width >= 1 && d.height >= 1 && d.width <= CFT_JPEG_MAX_SIDE && d.height <= CFT_JPEG_MAX_SIDE, "cft_jpeg_encode_coef: image size out of range");
-    CFT_REQUIRE(d.ncomp == 1 || d.ncomp == 3, "cft_jpeg_encode_coef: 1 or 3 components");
-    CFT_REQUIRE(enc_sampling_ok(d.ncomp, d.hmax, d.vmax), "cft_jpeg_encode_coef: sampling outside 1x1 (one component) and luma 1x1, 2x1, 2x2");
+    long blocks;
+    JPEG_REQUIRE_GEOMETRY("cft_jpeg_encode_coef", d, blocks);
     CFT_REQUIRE(d.src_stride >= (long)d.ncomp * d.width, "cft_jpeg_encode_coef: bad source row stride");
-    const int mx = (d.width + 8 * d.hmax - 1) / (8 * d.hmax), my = (d.height + 8 * d.vmax - 1) / (8 * d.vmax);
-    long blocks = 0;
-    for (int c = 0; c < 3; ++c) {
-      const int bw = c >= d.ncomp ? 0 : (c ? mx : mx * d.hmax), bh = c >= d.ncomp ? 0 : (c ? my : my * d.vmax);
-      CFT_REQUIRE(d.bw[c] == bw && d.bh[c] == bh, "cft_jpeg_encode_coef: block grid does not belong to this size and sampling");
-      blocks += (long)bw * bh;
-    }
     for (int k = 0; k < 64 * d.ncomp; ++k)
       CFT_REQUIRE(d.qtab_host[k] >= 1 && d.qtab_host[k] <= 255, "cft_jpeg_encode_coef: quantisation table entry outside 1..255");
     max_blocks = blocks > max_blocks ? blocks : max_blocks;
   }
-  hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)((max_blocks + ENC_WG_BLOCKS - 1) / ENC_WG_BLOCKS), n), dim3(ENC_THREADS), 0, as_stream(stream),
+  hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)((max_blocks + JPEG_WG_BLOCKS - 1) / JPEG_WG_BLOCKS), n), dim3(JPEG_THREADS), 0, as_stream(stream),
                      static_cast<const cft_jpeg_enc_desc_t*>(table_dev));
   return cft_check_launch("jpeg_fdct_kernel");
 }

@@ -80,13 +80,6 @@ def _save_image(path, array):
     Image.fromarray(array).save(path)
 
 
-def _save_jpeg(path, job, k):
-    """Pool job of ``device_jpeg``: wait for the batch's coefficient copy, code image ``k`` of the job, write the file."""
-    data = job.file_bytes(k)
-    with open(path, 'wb') as f:
-        f.write(data)
-
-
 def boxes_and_render(dets, counts, shapes, img_hw, originals, renderer, nc):
     """The device stage of one batch: ``cft_detect_boxes`` and, with a ``renderer``, ``cft_detect_render`` into ``originals``.  Returns
     ``(boxes, hist, flag)`` on the device.  No synchronisation with the host."""
@@ -181,9 +174,9 @@ def detect(opt, model=None, log=print, record=None):
                     save_path = str(save_dir / p.name)
                     stem, ext = save_path.rsplit('.', 1) if '.' in p.name else (save_path, 'jpg')
                     log(stem + '_rgb.' + ext)
-                    if on_device[b]:
-                        jobs.append(pool.submit(_save_jpeg, stem + '_rgb.' + ext, job, job_slot[b]))
-                        jobs.append(pool.submit(_save_jpeg, stem + '_ir.' + ext, job, job_slot[b] + 1))
+                    if on_device[b]:                                              # the pool waits for the coefficient copy, codes, writes
+                        jobs.append(pool.submit(job.save, job_slot[b], stem + '_rgb.' + ext))
+                        jobs.append(pool.submit(job.save, job_slot[b] + 1, stem + '_ir.' + ext))
                     else:
                         jobs.append(pool.submit(_save_image, stem + '_rgb.' + ext, drawn[b, 0]))
                         jobs.append(pool.submit(_save_image, stem + '_ir.' + ext, drawn[b, 1]))

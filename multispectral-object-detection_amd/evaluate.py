@@ -79,9 +79,7 @@ def _save_mosaics_coded(job, event, flag, files):
     if flag is not None:
         check_mosaic_flag(int(flag[0]))
     for k, f in enumerate(files):
-        data = job.file_bytes(k)
-        with open(f, 'wb') as fh:
-            fh.write(data)
+        job.save(k, f)
 
 
 def _plot_batch(pool, img, targets, paths, fname, names, device_jpeg=False):

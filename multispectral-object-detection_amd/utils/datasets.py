@@ -549,7 +549,7 @@ class PairLoader:
         the originals land in ``staged`` where ``_upload`` would have copied them and never exist on the host.  Any other file - not a
         JPEG, outside the subset, refused by the entropy decoder - is decoded by PIL into the pinned image staging as before and uploaded
         with the rest in a second copy.  Same return value as ``_upload``."""
-        from .jpeg import JPEG_DESC, QTAB_BYTES, fill_desc, jpeg_decode_u8, jpeg_entropy
+        from .jpeg import JPEG_DESC, decode_plan, entropy_staged, fill_decode_rows, jpeg_decode_u8
         ds = self.dataset
         files = [(i, (ds.img_files_rgb, ds.img_files_ir)[s][i]) for i in missing for s in (0, 1)]
         probed = []                                                  # (bytes or None, info or None) per file; the header is parsed once per file
@@ -560,17 +560,15 @@ class PairLoader:
                 probed.append(_probe_jpeg(f))
                 ds.jpeg_infos[f] = probed[-1][1]
         offs, total = [], 0                                          # the originals in staged, as _upload lays them out
-        joffs, jtotal, planes = [], _align16(len(files) * JPEG_DESC.itemsize), 0
         for (i, f), (blob, info) in zip(files, probed):
             w0, h0 = (int(v) for v in ds.shapes_rgb[i])
             if info is not None and (int(info["width"]), int(info["height"])) != (w0, h0):
                 raise ValueError(f'{f}: decodes to {int(info["width"])}x{int(info["height"])}, scanned as {w0}x{h0}')
             offs.append(total)
             total += _align16(h0 * w0 * 3)
-            joffs.append(jtotal)
-            if info is not None:
-                jtotal += _align16(2 * int(info["ncoef"])) + QTAB_BYTES
-                planes += _align16(int(info["plane_bytes"]))
+        infos = [info for _, info in probed]
+        plan = decode_plan(infos, reserve=len(files) * JPEG_DESC.itemsize)   # the table rows lead the JPEG upload
+        jtotal, planes = plan.upload_bytes, plan.plane_total
         slot.reserve(total, nrows, self.device)
         slot.reserve_jpeg(jtotal, jtotal + planes, self.device)
         staged = torch.empty(total, dtype=torch.uint8, device=self.device) if ds.cache_images else slot.staged
@@ -583,9 +581,7 @@ class PairLoader:
                 if blob is None:
                     with open(f, 'rb') as fh:
                         blob = fh.read()
-                nc = 2 * int(info["ncoef"])
-                q0 = joffs[k] + _align16(nc)
-                if jpeg_entropy(blob, info, jhost[joffs[k]:joffs[k] + nc].view(np.int16), jhost[q0:q0 + QTAB_BYTES].view(np.uint16)):
+                if entropy_staged(blob, info, jhost, plan, k):
                     return True
             im = decode_image(f)
             w0, h0 = (int(v) for v in ds.shapes_rgb[i])
@@ -604,12 +600,7 @@ class PairLoader:
             staged[lo:hi].copy_(slot.pinned[lo:hi], non_blocking=True)
         if live:
             table = np.zeros(len(live), dtype=JPEG_DESC)
-            plane_off = 0
-            for row, k in zip(table, live):
-                info = probed[k][1]
-                coef = slot.jstaged.data_ptr() + joffs[k]
-                fill_desc(row, info, coef, coef + _align16(2 * int(info["ncoef"])), staged.data_ptr() + offs[k], 3 * int(info["width"]), plane_off)
-                plane_off += _align16(int(info["plane_bytes"]))
+            fill_decode_rows(table, plan, infos, live, slot.jstaged.data_ptr(), [(staged.data_ptr() + offs[k], 3 * int(infos[k]["width"])) for k in live])
             nb = len(live) * JPEG_DESC.itemsize
             jhost[:nb] = table.view(np.uint8).reshape(-1)
             slot.jstaged[:jtotal].copy_(slot.jpinned[:jtotal], non_blocking=True)

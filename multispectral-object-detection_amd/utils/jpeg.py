@@ -8,6 +8,7 @@ PIL's ``save(f, 'JPEG', quality=q, subsampling=s)`` writes - one table upload, o
 of the coefficients into pinned memory, then ``cft_jpeg_write`` (headers and Huffman coding) on a pool of host threads;
 ``encode_jpeg_start`` / ``EncodeJob`` is the form that lets a caller overlap the copy and the coding with other work."""
 import ctypes
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -78,26 +79,73 @@ def jpeg_entropy(blob, info, coef, qtab):
     return True
 
 
+def fill_geometry(row, info):
+    """The geometry fields both tables share (JPEG_DESC, JPEG_ENC_DESC), copied from a file's info into one row."""
+    for k in ("width", "height", "ncomp", "hmax", "vmax", "bw", "bh"):
+        row[k] = info[k]
+
+
 def fill_desc(row, info, coef_ptr, qtab_ptr, dst_ptr, dst_stride, plane_off):
     """One JPEG_DESC row from a file's info and where its pieces live on the device."""
     row["coef"], row["qtab"], row["dst"], row["dst_stride"], row["plane_off"] = coef_ptr, qtab_ptr, dst_ptr, dst_stride, plane_off
-    for k in ("width", "height", "ncomp", "hmax", "vmax", "bw", "bh"):
-        row[k] = info[k]
+    fill_geometry(row, info)
+
+
+def _check_tables(who, table_dev, table_host, n, itemsize):
+    if not table_dev.is_cuda or table_host.is_cuda:
+        raise RuntimeError(f"{who}: table_dev lives on the device, table_host on the host (this package runs on MI355X only)")
+    for t in (table_dev, table_host):
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < n * itemsize:
+            raise ValueError(f"{who}: a table is a contiguous uint8 tensor of at least {n} x {itemsize} bytes")
 
 
 def jpeg_decode_u8(table_dev, table_host, n, workspace):
     """Launch ``cft_jpeg_decode_u8`` on the current stream: ``table_dev`` / ``table_host`` uint8 tensors holding the same ``n`` JPEG_DESC
     rows on the device and on the host, ``workspace`` a uint8 CUDA tensor for the component planes."""
-    if not table_dev.is_cuda or not workspace.is_cuda or table_host.is_cuda:
-        raise RuntimeError("jpeg_decode_u8: table_dev and workspace live on the device, table_host on the host (this package runs on MI355X only)")
-    for t in (table_dev, table_host):
-        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < n * JPEG_DESC.itemsize:
-            raise ValueError(f"jpeg_decode_u8: a table is a contiguous uint8 tensor of at least {n} x {JPEG_DESC.itemsize} bytes")
+    _check_tables("jpeg_decode_u8", table_dev, table_host, n, JPEG_DESC.itemsize)
+    if not workspace.is_cuda:
+        raise RuntimeError("jpeg_decode_u8: workspace lives on the device (this package runs on MI355X only)")
     if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
         raise ValueError("jpeg_decode_u8: workspace must be a contiguous uint8 tensor")
     st = _lib.load().cft_jpeg_decode_u8(table_dev.data_ptr(), table_host.data_ptr(), n, workspace.data_ptr(), workspace.numel(),
                                         torch.cuda.current_stream(workspace.device).cuda_stream)
     _lib.check(st, "cft_jpeg_decode_u8")
+
+
+# Where the files of one decode call sit: coef_off / qtab_off per file in the pinned upload (None for a file PIL decodes), upload_bytes
+# its size, plane_bytes per file in the plane workspace (0 for PIL's) and their sum plane_total.
+DecodePlan = namedtuple("DecodePlan", "coef_off qtab_off upload_bytes plane_bytes plane_total")
+
+
+def decode_plan(infos, reserve=0):
+    """The staging plan of ``infos`` (``jpeg_info`` records, None for a file PIL has to decode): ``reserve`` bytes for the caller's table
+    rows, then per file the coefficients and the quantisation tables, every offset and plane size a multiple of 16 (the C guards)."""
+    coef_off, qtab_off, plane_bytes, total = [], [], [], _align16(reserve)
+    for info in infos:
+        if info is None:
+            coef_off.append(None), qtab_off.append(None), plane_bytes.append(0)
+            continue
+        coef_off.append(total)
+        qtab_off.append(total + _align16(2 * int(info["ncoef"])))
+        total = qtab_off[-1] + QTAB_BYTES
+        plane_bytes.append(_align16(int(info["plane_bytes"])))
+    return DecodePlan(coef_off, qtab_off, total, plane_bytes, sum(plane_bytes))
+
+
+def entropy_staged(blob, info, host, plan, k):
+    """``jpeg_entropy`` of file ``k`` of the plan into its place in ``host``, the uint8 numpy view of the pinned upload."""
+    c0, q0 = plan.coef_off[k], plan.qtab_off[k]
+    return jpeg_entropy(blob, info, host[c0:c0 + 2 * int(info["ncoef"])].view(np.int16), host[q0:q0 + QTAB_BYTES].view(np.uint16))
+
+
+def fill_decode_rows(table, plan, infos, live, upload_ptr, dsts):
+    """The JPEG_DESC rows of the files ``live`` (indices into the plan), the upload at the device address ``upload_ptr``, ``dsts`` the
+    ``(pointer, row stride)`` of each destination.  Their planes follow one another from 0; returns where the last one ends."""
+    plane_off = 0
+    for row, k, (dst_ptr, dst_stride) in zip(table, live, dsts):
+        fill_desc(row, infos[k], upload_ptr + plan.coef_off[k], upload_ptr + plan.qtab_off[k], dst_ptr, dst_stride, plane_off)
+        plane_off += plan.plane_bytes[k]
+    return plane_off
 
 
 def decode_jpeg_batch(blobs, device, out=None):
@@ -108,44 +156,27 @@ def decode_jpeg_batch(blobs, device, out=None):
     the device, the returned tensors are ordered after the decode on that stream."""
     device = torch.device(device)
     infos = [jpeg_info(b) for b in blobs]
-    offs, total = [], 0
-    for info in infos:
-        if info is None:
-            offs.append(None)
-            continue
-        offs.append(total)
-        total += _align16(2 * int(info["ncoef"])) + QTAB_BYTES
+    plan = decode_plan(infos)
     results = [None] * len(blobs)
-    if total == 0:
+    if plan.upload_bytes == 0:
         return results
-    pinned = torch.empty(total, dtype=torch.uint8).pin_memory()
+    pinned = torch.empty(plan.upload_bytes, dtype=torch.uint8).pin_memory()
     host = pinned.numpy()
-    live = []
-    for k, (blob, info, off) in enumerate(zip(blobs, infos, offs)):
-        if info is None:
-            continue
-        nc = 2 * int(info["ncoef"])
-        qoff = off + _align16(nc)
-        if jpeg_entropy(blob, info, host[off:off + nc].view(np.int16), host[qoff:qoff + QTAB_BYTES].view(np.uint16)):
-            live.append(k)
+    live = [k for k, info in enumerate(infos) if info is not None and entropy_staged(blobs[k], info, host, plan, k)]
     if not live:
         return results
     table = np.zeros(len(live), dtype=JPEG_DESC)
-    plane_total = sum(_align16(int(infos[k]["plane_bytes"])) for k in live)
     with torch.cuda.device(device):
         staged = pinned.to(device, non_blocking=True)
-        workspace = torch.empty(plane_total, dtype=torch.uint8, device=device)
-        plane_off = 0
-        for row, k in zip(table, live):
-            info = infos[k]
-            h, w = int(info["height"]), int(info["width"])
+        dsts = []
+        for k in live:
+            h, w = int(infos[k]["height"]), int(infos[k]["width"])
             dst = out[k] if out is not None and out[k] is not None else torch.empty((h, w, 3), dtype=torch.uint8, device=device)
             if dst.dtype != torch.uint8 or tuple(dst.shape) != (h, w, 3) or dst.stride(2) != 1 or dst.stride(1) != 3 or dst.device != staged.device:
                 raise ValueError(f"decode_jpeg_batch: out[{k}] must be a uint8 [{h}, {w}, 3] tensor on {device} with contiguous pixels")
-            base = staged.data_ptr() + offs[k]
-            fill_desc(row, info, base, base + _align16(2 * int(info["ncoef"])), dst.data_ptr(), dst.stride(0) if h > 1 else max(dst.stride(0), 3 * w), plane_off)
-            plane_off += _align16(int(info["plane_bytes"]))
+            dsts.append((dst.data_ptr(), dst.stride(0) if h > 1 else max(dst.stride(0), 3 * w)))
             results[k] = dst
+        workspace = torch.empty(fill_decode_rows(table, plan, infos, live, staged.data_ptr(), dsts), dtype=torch.uint8, device=device)
         table_host = torch.from_numpy(table.view(np.uint8).reshape(-1)).pin_memory()
         table_dev = table_host.to(device, non_blocking=True)
         jpeg_decode_u8(table_dev, table_host, len(live), workspace)
@@ -198,11 +229,7 @@ def jpeg_write(coef, qtab, info):
 def jpeg_encode_coef(table_dev, table_host, n):
     """Launch ``cft_jpeg_encode_coef`` on the current stream: ``table_dev`` / ``table_host`` uint8 tensors holding the same ``n``
     JPEG_ENC_DESC rows on the device and on the host."""
-    if not table_dev.is_cuda or table_host.is_cuda:
-        raise RuntimeError("jpeg_encode_coef: table_dev lives on the device, table_host on the host (this package runs on MI355X only)")
-    for t in (table_dev, table_host):
-        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < n * JPEG_ENC_DESC.itemsize:
-            raise ValueError(f"jpeg_encode_coef: a table is a contiguous uint8 tensor of at least {n} x {JPEG_ENC_DESC.itemsize} bytes")
+    _check_tables("jpeg_encode_coef", table_dev, table_host, n, JPEG_ENC_DESC.itemsize)
     st = _lib.load().cft_jpeg_encode_coef(table_dev.data_ptr(), table_host.data_ptr(), n, torch.cuda.current_stream(table_dev.device).cuda_stream)
     _lib.check(st, "cft_jpeg_encode_coef")
 
@@ -230,6 +257,12 @@ class EncodeJob:
 
     def file_bytes(self, k):
         return jpeg_write(self.coefficients(k), self.qtab, self.infos[k])
+
+    def save(self, k, path):
+        """Code image ``k`` and write the file ``path``."""
+        data = self.file_bytes(k)
+        with open(path, 'wb') as f:
+            f.write(data)
 
     def all_bytes(self, pool=None):
         if pool is not None:
@@ -284,8 +317,7 @@ def encode_jpeg_start(images, quality=75, subsampling="4:2:0"):
             h, w, nc = im.shape
             row["src"], row["qtab"], row["qtab_host"], row["coef"] = im.data_ptr(), staged.data_ptr(), staging.data_ptr(), coef.data_ptr() + 2 * off
             row["src_stride"] = im.stride(0) if h > 1 else max(im.stride(0), nc * w)
-            for key in ("width", "height", "ncomp", "hmax", "vmax", "bw", "bh"):
-                row[key] = info[key]
+            fill_geometry(row, info)
             row["reserved"] = 0
         staged.copy_(staging, non_blocking=True)
         jpeg_encode_coef(staged[QTAB_BYTES:], staging[QTAB_BYTES:], n)

@@ -357,9 +357,8 @@ def plot_images(images, targets, paths=None, fname='images.jpg', names=None, max
         job = encode_jpeg_start(list(mosaics))
         if flag is not None:
             check_mosaic_flag(int(flag.item()))
-        for data, f in zip(job.all_bytes(), mosaic_file_names(fname, len(job))):
-            with open(f, 'wb') as fh:
-                fh.write(data)
+        for k, f in enumerate(mosaic_file_names(fname, len(job))):
+            job.save(k, f)
     elif fname:
         host = [m.cpu() for m in mosaics]
         if flag is not None:

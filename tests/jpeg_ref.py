@@ -7,6 +7,8 @@ import sys
 
 import numpy as np
 
+from jpeg_enc_ref import content  # noqa: F401  (the encoder's generator of [h, w, 3] uint8 test images; CONTENTS below are three of its kinds)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -16,19 +18,6 @@ CONTENTS = ("gradient", "noise", "mixed")
 LAYOUTS = ("444", "422", "420", "gray")
 OPTIONS = ({}, {"restart_marker_blocks": 1}, {"optimize": True})
 QUALITIES = (30, 75, 95, 100)
-
-
-def content(kind, h, w, seed):
-    """An [h, w, 3] uint8 test image."""
-    rng = np.random.RandomState(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    grad = np.stack([(xx * 255) // max(w - 1, 1), (yy * 255) // max(h - 1, 1), ((xx + yy) * 255) // max(h + w - 2, 1)], -1).astype(np.uint8)
-    noise = rng.randint(0, 256, (h, w, 3)).astype(np.uint8)
-    if kind == "gradient":
-        return grad
-    if kind == "noise":
-        return noise
-    return np.where(((xx // 4 + yy // 4) % 2 == 0)[..., None], grad, noise).astype(np.uint8)
 
 
 def encode(arr, layout, quality, **options):

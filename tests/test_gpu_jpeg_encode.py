@@ -55,8 +55,7 @@ def _encode_table(dev, cases, views):
         qi = qualities.index(c[3])
         row["src"], row["coef"], row["src_stride"] = v.data_ptr(), coef.data_ptr() + 2 * int(off), max(v.stride(0), v.shape[1] * int(info["ncomp"]))
         row["qtab"], row["qtab_host"] = tabs_dev.data_ptr() + 384 * qi, tabs_host.data_ptr() + 384 * qi
-        for key in ("width", "height", "ncomp", "hmax", "vmax", "bw", "bh"):
-            row[key] = info[key]
+        J.fill_geometry(row, info)
     host = torch.from_numpy(table.view(np.uint8).reshape(-1)).pin_memory()
     return host, host.to(dev), coef, offsets, infos, (tabs_host, tabs_dev, table)
 

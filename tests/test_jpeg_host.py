@@ -141,6 +141,46 @@ def test_many_threads_decode_side_by_side():
         assert np.array_equal(g, want), name
 
 
+@pytest.mark.parametrize("reserve", [0, 10 * 96 + 8])
+def test_decode_plan_meets_the_guards_of_decode_u8(reserve):
+    """The staging plan and the row filler give cft_jpeg_decode_u8 what its guards demand: 16-byte aligned, disjoint ranges inside the
+    upload behind the reserved prefix, and planes that ascend from 0 in multiples of 16 without overlap up to the plane total."""
+    picked = {}
+    for name, blob, _ in R.matrix():
+        size, _, layout, opt, q = name.split("-")
+        if size in ("1x1", "64x64") and opt == "opt0" and q == "q75":
+            picked.setdefault((size, layout), blob)
+    assert len(picked) == 2 * len(R.LAYOUTS)
+    infos = [J.jpeg_info(b) for b in picked.values()]
+    infos[3:3] = [None]
+    infos.append(None)
+    plan = J.decode_plan(infos, reserve)
+    live = [k for k, info in enumerate(infos) if info is not None]
+    ranges = [(0, reserve)]
+    for k, info in enumerate(infos):
+        if info is None:
+            assert plan.coef_off[k] is None and plan.qtab_off[k] is None and plan.plane_bytes[k] == 0
+            continue
+        ranges += [(plan.coef_off[k], plan.coef_off[k] + 2 * int(info["ncoef"])), (plan.qtab_off[k], plan.qtab_off[k] + J.QTAB_BYTES)]
+        assert plan.plane_bytes[k] % 16 == 0 and plan.plane_bytes[k] >= int(info["plane_bytes"])
+    assert all(lo % 16 == 0 and 0 <= lo <= hi <= plan.upload_bytes for lo, hi in ranges)
+    ranges.sort()
+    assert all(a[1] <= b[0] for a, b in zip(ranges, ranges[1:]))
+    assert plan.plane_total == sum(plan.plane_bytes)
+    upload, dsts = 0x7F0000001000, [(0x7E0000000000 + 0x100000 * j, 3 * int(infos[k]["width"]) + 5 * j) for j, k in enumerate(live)]
+    table = np.zeros(len(live), dtype=J.JPEG_DESC)
+    assert J.fill_decode_rows(table, plan, infos, live, upload, dsts) == plan.plane_total
+    end = 0
+    for row, k in zip(table, live):
+        assert int(row["plane_off"]) % 16 == 0 and int(row["plane_off"]) >= end
+        end = int(row["plane_off"]) + int(infos[k]["plane_bytes"])
+    assert end <= plan.plane_total and int(table[-1]["plane_off"]) + plan.plane_bytes[live[-1]] == plan.plane_total
+    want = np.zeros(len(live), dtype=J.JPEG_DESC)
+    for row, got, k, (dst, stride) in zip(want, table, live, dsts):
+        J.fill_desc(row, infos[k], upload + plan.coef_off[k], upload + plan.qtab_off[k], dst, stride, int(got["plane_off"]))
+    assert want.tobytes() == table.tobytes()
+
+
 def test_dataset_switch():
     """``decode`` is an attribute set in the constructor body, 'pil' by default, switched by use_device_jpeg on a dataset or a loader."""
     from msod_amd.utils import datasets as D

@@ -93,25 +93,15 @@ def device_part(blobs, runs):
     import torch
     dev = torch.device("cuda:0")
     infos = [J.jpeg_info(b) for b in blobs]
-    offs, total = [], 0
-    for i in infos:
-        offs.append(total)
-        total += J._align16(2 * int(i["ncoef"])) + J.QTAB_BYTES
+    plan = J.decode_plan(infos)
+    total = plan.upload_bytes
     pinned = torch.empty(total, dtype=torch.uint8).pin_memory()
-    host = pinned.numpy()
-    table = np.zeros(len(blobs), dtype=J.JPEG_DESC)
-    planes = 0
+    for k, (b, i) in enumerate(zip(blobs, infos)):
+        assert J.entropy_staged(b, i, pinned.numpy(), plan, k)
     staged = pinned.to(dev)
-    outs = []
-    for row, b, i, o in zip(table, blobs, infos, offs):
-        nc = 2 * int(i["ncoef"])
-        q0 = o + J._align16(nc)
-        assert J.jpeg_entropy(b, i, host[o:o + nc].view(np.int16), host[q0:q0 + J.QTAB_BYTES].view(np.uint16))
-        dst = torch.empty((int(i["height"]), int(i["width"]), 3), dtype=torch.uint8, device=dev)
-        outs.append(dst)
-        J.fill_desc(row, i, staged.data_ptr() + o, staged.data_ptr() + q0, dst.data_ptr(), dst.stride(0), planes)
-        planes += J._align16(int(i["plane_bytes"]))
-    staged.copy_(pinned)
+    outs = [torch.empty((int(i["height"]), int(i["width"]), 3), dtype=torch.uint8, device=dev) for i in infos]
+    table = np.zeros(len(blobs), dtype=J.JPEG_DESC)
+    planes = J.fill_decode_rows(table, plan, infos, range(len(blobs)), staged.data_ptr(), [(o.data_ptr(), o.stride(0)) for o in outs])
     table_host = torch.from_numpy(table.view(np.uint8).reshape(-1)).pin_memory()
     table_dev = table_host.to(dev)
     ws = torch.empty(planes, dtype=torch.uint8, device=dev)

@@ -127,8 +127,7 @@ def device_part(imgs, runs):
     table = np.zeros(len(flat), dtype=J.JPEG_ENC_DESC)
     for k, (row, t, info) in enumerate(zip(table, flat, infos)):
         row["src"], row["qtab"], row["qtab_host"], row["coef"], row["src_stride"] = t.data_ptr(), tabs_dev.data_ptr(), tabs_host.data_ptr(), coef.data_ptr() + 2 * per * k, t.stride(0)
-        for key in ("width", "height", "ncomp", "hmax", "vmax", "bw", "bh"):
-            row[key] = info[key]
+        J.fill_geometry(row, info)
     table_host = torch.from_numpy(table.view(np.uint8).reshape(-1)).pin_memory()
     table_dev = table_host.to(dev)
     enc = _event_ms(lambda: J.jpeg_encode_coef(table_dev, table_host, len(flat)), runs)
