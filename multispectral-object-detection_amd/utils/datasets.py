@@ -3,7 +3,8 @@
 aspect ratio, pad with grey - on the device, one kernel per image (``cft_letterbox_u8``), and the pair packer that
 builds the uint8 ``[B,6,H,W]`` batch the model consumes (``utils/datasets.py:1274-1281``: BGR->RGB, HWC->CHW); below them the paired
 RGB + IR dataset and its loaders, validation form (one cft_pair_batch_u8 launch per batch) and augmented training form (one
-cft_augment_batch_u8 launch per batch), and the inference loaders of the detect driver."""
+cft_augment_batch_u8 launch per batch), and the inference loaders of the detect driver.  The three batched loaders share one prefetch
+pipeline (``_Prefetch``, described where it is defined) and one decode-and-upload (``_upload``); each states only its table and launch."""
 import glob
 import os
 from pathlib import Path
@@ -325,51 +326,70 @@ class LoadMultiModalImagesAndLabels:  # for testing
 
     def _check_sizes(self, prefix=''):
         """The INTER_AREA resize of cft_pair_batch_u8 reduces by at most CFT_PAIR_MAX_REDUCTION per axis: say so before any work."""
-        img_size = self.img_size
-        for f, (w0, h0) in zip(self.img_files_rgb, self.shapes_rgb.astype(int)):
-            r = img_size / max(h0, w0)
-            if r < 1 and (int(h0 * r) * PAIR_MAX_REDUCTION < h0 or int(w0 * r) * PAIR_MAX_REDUCTION < w0):
-                raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={img_size} would reduce it by more than {PAIR_MAX_REDUCTION}x per axis, '
+        for index, f in enumerate(self.img_files_rgb):
+            h0, w0 = self.original_size(index)
+            h, w = self.resized_size(h0, w0)
+            if h * PAIR_MAX_REDUCTION < h0 or w * PAIR_MAX_REDUCTION < w0:
+                raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={self.img_size} would reduce it by more than {PAIR_MAX_REDUCTION}x per axis, '
                                  f'which cft_pair_batch_u8 does not do; use a larger img_size (about {-(-max(h0, w0) // PAIR_MAX_REDUCTION)} or more) or smaller images')
 
     def __len__(self):
         return len(self.img_files_rgb)
 
+    def original_size(self, index):
+        """(h0, w0) of pair ``index`` as scanned."""
+        w0, h0 = (int(v) for v in self.shapes_rgb[index])
+        return h0, w0
+
+    def resized_size(self, h0, w0):
+        """(h, w) of load_image_rgb_ir (:1361-1367)."""
+        r = self.img_size / max(h0, w0)  # ratio
+        return (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
+
+    def letterbox_shape(self, index):
+        """The final letterboxed shape of pair ``index``: its batch's rect shape, or ``img_size``."""
+        return self.batch_shapes_rgb[self.batch_rgb[index]] if self.rect else self.img_size
+
+    def _letterbox(self, index, scaleup):
+        """The resize of load_image_rgb_ir followed by ``letterbox(auto=False, scaleup=scaleup)``:
+        ``(h0, w0, h, w, top, left, (H, W), ratio, pad, new_unpad)``."""
+        h0, w0 = self.original_size(index)
+        h, w = self.resized_size(h0, w0)
+        new_unpad, ratio, pad, (top, bottom, left, right) = letterbox_geometry((h, w), self.letterbox_shape(index), auto=False, scaleup=scaleup)
+        return h0, w0, h, w, top, left, (new_unpad[1] + top + bottom, new_unpad[0] + left + right), ratio, pad, new_unpad
+
     def pair_geometry(self, index):
         """Where pair ``index`` lands in its batch: ``(h0, w0, h, w, top, left, mode, (H, W), ratio, pad)`` - the size arithmetic of
         load_image_rgb_ir (:1361-1367) and of ``letterbox(auto=False, scaleup=False)`` (:1205-1207).  ``ratio`` is the letterbox's own:
         (1, 1) for every shape this class builds, and then ``(h, w)`` is what lands at ``(top, left)``; ``build_descriptors`` checks it."""
-        w0, h0 = (int(v) for v in self.shapes_rgb[index])
+        h0, w0, h, w, top, left, HW, ratio, pad, _ = self._letterbox(index, scaleup=False)
         r = self.img_size / max(h0, w0)  # ratio
-        h, w = (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
         mode = PAIR_COPY if r == 1 else (PAIR_AREA if r < 1 else PAIR_LINEAR)
-        shape = self.batch_shapes_rgb[self.batch_rgb[index]] if self.rect else self.img_size  # final letterboxed shape
-        new_unpad, ratio, pad, (top, bottom, left, right) = letterbox_geometry((h, w), shape, auto=False, scaleup=False)
-        return h0, w0, h, w, top, left, mode, (new_unpad[1] + top + bottom, new_unpad[0] + left + right), ratio, pad
+        return h0, w0, h, w, top, left, mode, HW, ratio, pad
+
+    def _letterboxed_labels(self, index, h0, w0, h, w, ratio, pad):
+        """``(labels [nL, 5] float32 in pixel xyxy, shapes)`` of a pair that is letterboxed on its own (:1209-1213)."""
+        labels = self.labels_rgb[index].copy()
+        if labels.size:  # normalized xywh to pixel xyxy format
+            labels[:, 1:] = xywhn2xyxy(labels[:, 1:], ratio[0] * w, ratio[1] * h, padw=pad[0], padh=pad[1])
+        return labels, ((h0, w0), ((h / h0, w / w0), pad))  # for COCO mAP rescaling
 
     def item_targets(self, index):
         """``(labels_out [nL, 6] float32 with column 0 zero, shapes)`` of ``__getitem__`` (:1209-1213, :1243-1247, :1266-1268)."""
         h0, w0, h, w, top, left, mode, (H, W), ratio, pad = self.pair_geometry(index)
-        shapes = (h0, w0), ((h / h0, w / w0), pad)  # for COCO mAP rescaling
-        labels = self.labels_rgb[index].copy()
-        if labels.size:  # normalized xywh to pixel xyxy format
-            labels[:, 1:] = xywhn2xyxy(labels[:, 1:], ratio[0] * w, ratio[1] * h, padw=pad[0], padh=pad[1])
-        nL = len(labels)  # number of labels
-        if nL:
-            labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])  # convert xyxy to xywh
-            labels[:, [2, 4]] /= H  # normalized height 0-1
-            labels[:, [1, 3]] /= W  # normalized width 0-1
-        labels_out = torch.zeros((nL, 6))
-        if nL:
-            labels_out[:, 1:] = torch.from_numpy(labels)
-        return labels_out, shapes
+        labels, shapes = self._letterboxed_labels(index, h0, w0, h, w, ratio, pad)
+        return _labels_out(labels, H, W), shapes
 
-    def batch_targets(self, indices):
-        """``(targets [nt, 6] float32 CPU, paths, shapes)`` of one batch: ``item_targets`` + the reference's ``collate_fn`` (:1284-1288)."""
-        label, shapes = zip(*(self.item_targets(i) for i in indices))
+    def _collate(self, label, indices, shapes):
+        """The reference's ``collate_fn`` (:1284-1288) on the ``labels_out`` of the pairs ``indices``: ``(targets, paths, shapes)``."""
         for i, l in enumerate(label):
             l[:, 0] = i  # add target image index for build_targets()
-        return torch.cat(label, 0), tuple(self.img_files_rgb[i] for i in indices), shapes
+        return torch.cat(label, 0), tuple(self.img_files_rgb[i] for i in indices), tuple(shapes)
+
+    def batch_targets(self, indices):
+        """``(targets [nt, 6] float32 CPU, paths, shapes)`` of one batch: ``item_targets`` + the reference's ``collate_fn``."""
+        label, shapes = zip(*(self.item_targets(i) for i in indices))
+        return self._collate(label, indices, shapes)
 
     def build_descriptors(self, indices, flip=0):
         """The table of cft_pair_batch_u8 for one batch, source pointers and strides left zero: ``(PAIR_DESC array [B], (H, W))``.
@@ -383,28 +403,72 @@ class LoadMultiModalImagesAndLabels:  # for testing
             if HW is not None and hw != HW:
                 raise AssertionError(f"pair {index}: letterbox {hw} differs from its batch's {HW}")
             HW = hw
-            row["h0"], row["w0"], row["h"], row["w"], row["top"], row["left"], row["mode"], row["flip"] = h0, w0, h, w, top, left, mode, flip
+            _fill_geometry(row, h0, w0, h, w, top, left, mode, flip)
         return desc, HW
 
     def load_pair(self, index):
         """The decoded originals of one pair, HWC RGB uint8 numpy arrays; checks them against the scanned shape."""
-        rgb, ir = decode_image(self.img_files_rgb[index]), decode_image(self.img_files_ir[index])
-        w0, h0 = (int(v) for v in self.shapes_rgb[index])
-        for im, f in ((rgb, self.img_files_rgb[index]), (ir, self.img_files_ir[index])):
-            if im.shape != (h0, w0, 3):
-                raise ValueError(f'{f}: decoded to {im.shape[1]}x{im.shape[0]}, scanned as {w0}x{h0}')
-        return rgb, ir
+        h0, w0 = self.original_size(index)
+        return _decode_checked(self.img_files_rgb[index], h0, w0), _decode_checked(self.img_files_ir[index], h0, w0)
+
+
+def _labels_out(labels, H, W, flipud=False, fliplr=False):
+    """The tail of ``__getitem__`` (:1243-1268): pixel xyxy labels [nL, 5] float32 (changed in place) to xywh normalised by the batch's
+    ``(H, W)``, the two label flips, and ``labels_out`` [nL, 6] float32 with column 0 zero."""
+    nL = len(labels)  # number of labels
+    if nL:
+        labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])  # convert xyxy to xywh
+        labels[:, [2, 4]] /= H  # normalized height 0-1
+        labels[:, [1, 3]] /= W  # normalized width 0-1
+        if flipud:
+            labels[:, 2] = 1 - labels[:, 2]
+        if fliplr:
+            labels[:, 1] = 1 - labels[:, 1]
+    labels_out = torch.zeros((nL, 6))
+    if nL:
+        labels_out[:, 1:] = torch.from_numpy(labels)
+    return labels_out
+
+
+def _decode_checked(path, h0, w0):
+    """``decode_image`` of a file whose header said ``w0`` x ``h0`` when it was scanned."""
+    im = decode_image(path)
+    if im.shape != (h0, w0, 3):
+        raise ValueError(f'{path}: decoded to {im.shape[1]}x{im.shape[0]}, scanned as {w0}x{h0}')
+    return im
+
+
+def _fill_geometry(row, h0, w0, h, w, top, left, mode, flip):
+    """The geometry fields of one PAIR_DESC row: ``h0 x w0`` resized to ``h x w`` by ``mode``, landing at ``(top, left)``."""
+    row["h0"], row["w0"], row["h"], row["w"], row["top"], row["left"], row["mode"], row["flip"] = h0, w0, h, w, top, left, mode, flip
+
+
+def _fill_source(row, rgb, ir, h0, w0):
+    """Source pointers and row strides of one table row or tile, after checking the pair against the size the table states."""
+    for t in (rgb, ir):
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.stride(2) != 1 or t.stride(1) != 3 or not t.is_cuda:
+            raise ValueError("pair sources must be HWC uint8 CUDA tensors with contiguous pixels")
+        if tuple(t.shape[:2]) != (h0, w0):
+            raise ValueError(f"pair source is {tuple(t.shape[:2])}, the table says {(h0, w0)}")
+    row["src_rgb"], row["src_ir"], row["stride_rgb"], row["stride_ir"] = rgb.data_ptr(), ir.data_ptr(), rgb.stride(0), ir.stride(0)
+
+
+def _launch_direct(launch, out, table, luts=None):
+    """The launch of the direct forms: the host table (and look-up tables) pinned, copied to ``out``'s device without blocking on the
+    current stream, then ``launch(table_dev, table_host, [luts_dev,] out)``."""
+    def upload(a):
+        host = torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
+        return host, host.to(out.device, non_blocking=True)
+    host, dev = upload(np.ascontiguousarray(table).view(np.uint8).reshape(len(table), -1))
+    launch(dev, host, *(() if luts is None else (upload(luts)[1],)), out)
+    return out
 
 
 def pair_batch(desc, out, color=114):
     """Launch cft_pair_batch_u8: ``desc`` is a filled PAIR_DESC array (host), ``out`` the uint8 CUDA [B, 6, H, W] batch to write.
     The device copy of the table is made on the current stream."""
     from ..ops import pair_batch_u8
-    desc = np.ascontiguousarray(desc)
-    host = torch.from_numpy(desc.view(np.uint8).reshape(len(desc), -1)).pin_memory()
-    dev = host.to(out.device, non_blocking=True)
-    pair_batch_u8(dev, host, out, color)
-    return out
+    return _launch_direct(lambda dev, host, out: pair_batch_u8(dev, host, out, color), out, desc)
 
 
 def assemble_batch(dataset, indices, device, sources=None):
@@ -429,33 +493,34 @@ def assemble_batch_by_pair(dataset, indices, sources):
     for k, (index, pair) in enumerate(zip(indices, sources)):
         h0, w0, h, w, _, _, mode, (H, W), _, _ = dataset.pair_geometry(index)
         desc = np.zeros(1, dtype=PAIR_DESC)
-        row = desc[0]
-        row["h0"], row["w0"], row["h"], row["w"], row["mode"], row["flip"] = h0, w0, h, w, mode, 1   # RGB in, BGR planes out
+        _fill_geometry(desc[0], h0, w0, h, w, 0, 0, mode, flip=1)   # RGB in, BGR planes out
         _fill_sources(desc, [pair])
         w4 = (w + 3) & ~3                                           # the kernel writes whole dwords of a row
         chw = pair_batch(desc, torch.empty((1, 6, h, w4), dtype=torch.uint8, device=pair[0].device))[0, :, :, :w]
         bgr, ir = chw[:3].permute(1, 2, 0).contiguous(), chw[3:].permute(1, 2, 0).contiguous()      # HWC BGR, what letterbox_pair takes
         if out is None:
             out = torch.empty((len(indices), 6, H, W), dtype=torch.uint8, device=pair[0].device)
-        shape = dataset.batch_shapes_rgb[dataset.batch_rgb[index]] if dataset.rect else dataset.img_size
+        shape = dataset.letterbox_shape(index)
         letterbox_pair(bgr, ir, tuple(int(v) for v in shape) if dataset.rect else shape, auto=False, scaleup=False, out=out[k])
     return out
 
 
 def _fill_sources(desc, sources):
     for row, (rgb, ir) in zip(desc, sources):
-        for t in (rgb, ir):
-            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.stride(2) != 1 or t.stride(1) != 3 or not t.is_cuda:
-                raise ValueError("pair sources must be HWC uint8 CUDA tensors with contiguous pixels")
-            if tuple(t.shape[:2]) != (int(row["h0"]), int(row["w0"])):
-                raise ValueError(f"pair source is {tuple(t.shape[:2])}, the table says {(int(row['h0']), int(row['w0']))}")
-        row["src_rgb"], row["src_ir"], row["stride_rgb"], row["stride_ir"] = rgb.data_ptr(), ir.data_ptr(), rgb.stride(0), ir.stride(0)
+        _fill_source(row, rgb, ir, int(row["h0"]), int(row["w0"]))
 
 
+# ------------------------------------------------------------------------------ the prefetch pipeline of the three loaders
+# PairLoader, AugmentedPairLoader and LoadImagePairs differ in what a batch is and in the kernel that assembles it; how a batch gets to
+# the device is one thing, stated here.  While batch k is assembled and used, batch k + 1 is staged: its files are decoded on a pool
+# of threads into pinned memory that is reused (``_upload``), and uploaded with its table on a side stream.  Two events per slot order
+# the two streams: ``ready``, recorded on the side stream after the uploads, is what the consumer stream waits on before the batch's
+# launch; ``consumed``, recorded on the consumer stream after that launch, is what the side stream waits on before it rewrites the
+# slot two batches later - the consumer stream may be many batches behind the host.
 class _Slot:
-    """One of the loader's two staging sets: pinned host bytes, their device copy, the table, and the two events that order them."""
+    """One of the pipeline's two staging sets: pinned host bytes, their device copy, the table, and the two events that order them."""
 
-    def __init__(self, row_bytes=PAIR_DESC.itemsize):
+    def __init__(self, row_bytes):
         self.row_bytes = row_bytes                 # bytes of table per batch row
         self.pinned = self.staged = self.desc_host = self.desc_dev = None
         self.jpinned = self.jstaged = None      # decode = 'device': table + coefficients + tables (pinned), the same + planes (device)
@@ -479,15 +544,142 @@ class _Slot:
         if self.jstaged is None or self.jstaged.numel() < device_bytes:
             self.jstaged = torch.empty(device_bytes, dtype=torch.uint8, device=device)
 
+    def upload_table(self, n, *parts):
+        """The host arrays ``parts``, one after the other, as the ``n`` rows of the table: written into the pinned copy and uploaded
+        without blocking (current = side stream)."""
+        host, at = self.desc_host[:n].view(-1).numpy(), 0
+        for part in parts:
+            raw = part.view(np.uint8).reshape(-1)
+            host[at:at + raw.size] = raw
+            at += raw.size
+        self.desc_dev[:n].copy_(self.desc_host[:n], non_blocking=True)
+
+
+class _Prefetch:
+    """The pipeline itself: the decode pool and the one-thread stager, the side stream, the two slots and the event protocol above.
+    ``run(batches, stage, assemble)`` yields ``(item, assemble(slot, item))`` per batch, where ``stage(batch, slot, pool)``, called on
+    the stager thread with the side stream current, fills the slot and returns ``(staged, item)``: the device buffer its originals
+    were uploaded to (None if there was no upload) and whatever ``assemble``, called on the consumer's thread and stream, needs."""
+
+    def __init__(self, device, workers, row_bytes=PAIR_DESC.itemsize):
+        self.device, self.workers = device, workers
+        self.side = None
+        self.slots = (_Slot(row_bytes), _Slot(row_bytes))
+
+    def run(self, batches, stage, assemble):
+        from concurrent.futures import ThreadPoolExecutor
+        if self.side is None:
+            self.side = torch.cuda.Stream(self.device)
+        batches = list(batches)
+
+        def staged_on_side(k, pool):
+            slot = self.slots[k % 2]
+            with torch.cuda.device(self.device), torch.cuda.stream(self.side):
+                # Whatever this does to the slot - the table always, the staging buffer when it is reused - comes after the launch that
+                # read the slot two batches ago.
+                if slot.consumed is not None:
+                    self.side.wait_event(slot.consumed)
+                staged = stage(batches[k], slot, pool)
+                slot.ready = torch.cuda.Event()
+                slot.ready.record(self.side)
+            return staged
+
+        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
+            nxt = stager.submit(staged_on_side, 0, pool) if batches else None
+            for k in range(len(batches)):
+                staged, item = nxt.result()
+                slot = self.slots[k % 2]
+                # the next batch decodes and uploads while this one is assembled and used
+                nxt = stager.submit(staged_on_side, k + 1, pool) if k + 1 < len(batches) else None
+                cur = torch.cuda.current_stream(self.device)
+                cur.wait_event(slot.ready)
+                out = assemble(slot, item)
+                slot.consumed = torch.cuda.Event()
+                slot.consumed.record(cur)
+                slot.desc_dev.record_stream(cur)                 # allocated on the side stream, read on this one
+                if staged is not None:
+                    staged.record_stream(cur)
+                yield item, out
+
+
+def _upload(entries, nrows, slot, pool, device, decode='pil', jpeg_infos=None, own_buffer=False):
+    """The files ``entries``, ``(path, (h0, w0) as scanned)`` each, as HWC RGB uint8 CUDA tensors: laid out one after the other, 16-byte
+    aligned, decoded on the pool and uploaded without blocking (current = side stream) into the slot's device buffer, or with
+    ``own_buffer`` into one allocated here, for originals that outlive the batch.  Each pool worker picks its file's decoder.  With
+    ``decode == 'device'`` a file the device decoder takes (``jpeg_infos`` remembers the verdict per path) is Huffman-decoded straight
+    into the slot's pinned JPEG staging - table rows, then per file coefficients and quantisation tables - which one copy uploads and
+    one cft_jpeg_decode_u8 call turns into pixels: those originals never exist on the host.  Every other file goes through PIL into
+    the pinned image staging, one copy; where no file qualifies there is no JPEG staging.  Also sizes the slot's table for ``nrows``.
+    Returns ``(staged, views, decoded)``: the device buffer (None without entries), and per entry its tensor and PIL's array (None
+    for a file decoded on the device)."""
+    from . import jpeg as J
+    sizes = [h0 * w0 * 3 for _, (h0, w0) in entries]
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + _align16(n))
+    total = offs.pop()
+    slot.reserve(total, nrows, device)
+    if not entries:
+        return None, [], []
+    probed = [(None, None)] * len(entries)                       # (bytes or None, info or None) per file; the header is parsed once per file
+    if decode == 'device':
+        for k, (f, (h0, w0)) in enumerate(entries):
+            if f in jpeg_infos:
+                probed[k] = (None, jpeg_infos[f])
+            else:
+                probed[k] = _probe_jpeg(f)
+                jpeg_infos[f] = probed[k][1]
+            info = probed[k][1]
+            if info is not None and (int(info["height"]), int(info["width"])) != (h0, w0):
+                raise ValueError(f'{f}: decodes to {int(info["width"])}x{int(info["height"])}, scanned as {w0}x{h0}')
+    infos = [info for _, info in probed]
+    plan = jhost = None
+    if any(info is not None for info in infos):
+        plan = J.decode_plan(infos, reserve=len(entries) * J.JPEG_DESC.itemsize)   # the table rows lead the JPEG upload
+        slot.reserve_jpeg(plan.upload_bytes, plan.upload_bytes + plan.plane_total, device)
+        jhost = slot.jpinned.numpy()
+    staged = torch.empty(total, dtype=torch.uint8, device=device) if own_buffer else slot.staged
+    host = slot.pinned.numpy()
+
+    def work(k):
+        """None: file k's coefficients are in the JPEG staging; else its PIL decode, which is in the image staging."""
+        (f, (h0, w0)), (blob, info) = entries[k], probed[k]
+        if info is not None:
+            if blob is None:
+                with open(f, 'rb') as fh:
+                    blob = fh.read()
+            if J.entropy_staged(blob, info, jhost, plan, k):
+                return None
+        im = _decode_checked(f, h0, w0)
+        host[offs[k]:offs[k] + im.nbytes] = im.reshape(-1)
+        return im
+
+    # two files a task: with one the PNG-bound loaders measured 8 - 12 % slower (profiles/loader_pipeline.md)
+    tasks = pool.map(lambda k: [work(j) for j in range(k, min(k + 2, len(entries)))], range(0, len(entries), 2))
+    decoded = [im for ims in tasks for im in ims]
+    live = [k for k, im in enumerate(decoded) if im is None]
+    by_pil = [k for k, im in enumerate(decoded) if im is not None]
+    if by_pil:
+        lo, hi = offs[by_pil[0]], offs[by_pil[-1]] + sizes[by_pil[-1]]
+        staged[lo:hi].copy_(slot.pinned[lo:hi], non_blocking=True)
+    if live:
+        table = np.zeros(len(live), dtype=J.JPEG_DESC)
+        J.fill_decode_rows(table, plan, infos, live, slot.jstaged.data_ptr(), [(staged.data_ptr() + offs[k], 3 * entries[k][1][1]) for k in live])
+        nb, jtotal = len(live) * J.JPEG_DESC.itemsize, plan.upload_bytes
+        jhost[:nb] = table.view(np.uint8).reshape(-1)
+        slot.jstaged[:jtotal].copy_(slot.jpinned[:jtotal], non_blocking=True)
+        J.jpeg_decode_u8(slot.jstaged[:nb], slot.jpinned[:nb], len(live), slot.jstaged[jtotal:jtotal + plan.plane_total])
+    views = [staged[o:o + n].view(h0, w0, 3) for o, n, (_, (h0, w0)) in zip(offs, sizes, entries)]
+    return staged, views, decoded
+
 
 class PairLoader:
     """The iterable ``create_dataloader_rgb_ir`` returns: yields ``(img6 uint8 cuda [B, 6, H, W], targets float32 CPU [nt, 6], paths,
-    shapes)`` per batch, in dataset order.  While a batch is in use the next one is decoded (PIL, a pool of ``workers`` threads),
-    staged into a reused pinned buffer and uploaded on a side stream; an event recorded there is what the consumer stream waits on
-    before the batch's single cft_pair_batch_u8 launch, and an event recorded after that launch is what the side stream waits on
-    before it overwrites the slot's table and staging buffer two batches later (cached batches included: they reuse the table).
-    With ``dataset.decode == 'device'`` (``use_device_jpeg``) the pool only Huffman-decodes the JPEG files and their pixels are made on
-    the side stream by one cft_jpeg_decode_u8 call per batch (``_upload_device``)."""
+    shapes)`` per batch, in dataset order.  Batches come through the prefetch pipeline above (``_Prefetch``: decode pool of ``workers``
+    threads, reused pinned staging, side stream, the ``ready`` / ``consumed`` events - cached batches included, they reuse the table);
+    what is stated here is the batch's table and its single cft_pair_batch_u8 launch.  With ``dataset.decode == 'device'``
+    (``use_device_jpeg``) the pool only Huffman-decodes the JPEG files and their pixels are made on the side stream (``_upload``)."""
+    ROW_BYTES = PAIR_DESC.itemsize                 # bytes of the slots' table per batch row
 
     def __init__(self, dataset, batch_size, workers=8, rank=-1, world_size=1, device=None):
         self.dataset = dataset
@@ -500,8 +692,7 @@ class PairLoader:
         else:
             self.batch_range = range(nb)
         self.device = torch.device(device if device is not None else "cuda")
-        self._side = None
-        self._slots = (_Slot(), _Slot())
+        self._pipe = _Prefetch(self.device, self.workers, self.ROW_BYTES)
 
     def __len__(self):
         return len(self.batch_range)
@@ -509,163 +700,48 @@ class PairLoader:
     def batch_indices(self, b):
         return list(range(b * self.batch_size, min((b + 1) * self.batch_size, len(self.dataset))))
 
-    def _upload(self, indices, nrows, slot, pool):
+    def _originals(self, indices, nrows, slot, pool):
         """The originals of the pairs ``indices`` (distinct) as HWC RGB uint8 CUDA tensors, ``{index: (rgb, ir)}``: cached ones as they
-        are, the others decoded on the pool, packed into the slot's pinned bytes and uploaded without blocking (current = side stream).
-        Also sizes the slot's table for ``nrows`` rows.  Returns ``(staged, by_index)``, ``staged`` the device buffer of this upload or None."""
+        are, the others through ``_upload``, RGB then IR per pair - with ``cache_images`` into a buffer of their own, since they stay.
+        Returns ``(staged, by_index)``, ``staged`` the device buffer of this upload or None."""
         ds = self.dataset
         by_index = {i: (ds.imgs_rgb[i], ds.imgs_ir[i]) for i in indices if ds.imgs_rgb[i] is not None}
         missing = [i for i in indices if i not in by_index]
-        if not missing:
-            slot.reserve(0, nrows, self.device)
-            return None, by_index
-        if ds.decode == 'device':
-            return self._upload_device(missing, by_index, nrows, slot, pool)
-        pairs = list(pool.map(ds.load_pair, missing))
-        offs, total = [], 0
-        for rgb, ir in pairs:
-            offs.append((total, total + _align16(rgb.nbytes)))
-            total += _align16(rgb.nbytes) + _align16(ir.nbytes)
-        slot.reserve(total, nrows, self.device)
-        if ds.cache_images:                      # these bytes stay: the batch's originals live in a buffer of their own
-            staged = torch.empty(total, dtype=torch.uint8, device=self.device)
-        else:
-            staged = slot.staged
-        host = slot.pinned.numpy()
-        for (o_rgb, o_ir), (rgb, ir) in zip(offs, pairs):
-            host[o_rgb:o_rgb + rgb.nbytes] = rgb.reshape(-1)
-            host[o_ir:o_ir + ir.nbytes] = ir.reshape(-1)
-        staged[:total].copy_(slot.pinned[:total], non_blocking=True)
-        for i, (o_rgb, o_ir), (rgb, ir) in zip(missing, offs, pairs):
-            by_index[i] = (staged[o_rgb:o_rgb + rgb.nbytes].view(rgb.shape), staged[o_ir:o_ir + ir.nbytes].view(ir.shape))
-            if ds.cache_images:
-                ds.imgs_rgb[i], ds.imgs_ir[i] = by_index[i]
-        return staged, by_index
-
-    def _upload_device(self, missing, by_index, nrows, slot, pool):
-        """``_upload`` with ``dataset.decode == 'device'``: every file of the pairs ``missing`` that the device decoder takes is read and
-        Huffman-decoded on the pool straight into the slot's pinned JPEG staging (table rows, then per file coefficients and quantisation
-        tables), uploaded in one copy and turned into its HWC RGB original by one cft_jpeg_decode_u8 call on the current (side) stream;
-        the originals land in ``staged`` where ``_upload`` would have copied them and never exist on the host.  Any other file - not a
-        JPEG, outside the subset, refused by the entropy decoder - is decoded by PIL into the pinned image staging as before and uploaded
-        with the rest in a second copy.  Same return value as ``_upload``."""
-        from .jpeg import JPEG_DESC, decode_plan, entropy_staged, fill_decode_rows, jpeg_decode_u8
-        ds = self.dataset
-        files = [(i, (ds.img_files_rgb, ds.img_files_ir)[s][i]) for i in missing for s in (0, 1)]
-        probed = []                                                  # (bytes or None, info or None) per file; the header is parsed once per file
-        for _, f in files:
-            if f in ds.jpeg_infos:
-                probed.append((None, ds.jpeg_infos[f]))
-            else:
-                probed.append(_probe_jpeg(f))
-                ds.jpeg_infos[f] = probed[-1][1]
-        offs, total = [], 0                                          # the originals in staged, as _upload lays them out
-        for (i, f), (blob, info) in zip(files, probed):
-            w0, h0 = (int(v) for v in ds.shapes_rgb[i])
-            if info is not None and (int(info["width"]), int(info["height"])) != (w0, h0):
-                raise ValueError(f'{f}: decodes to {int(info["width"])}x{int(info["height"])}, scanned as {w0}x{h0}')
-            offs.append(total)
-            total += _align16(h0 * w0 * 3)
-        infos = [info for _, info in probed]
-        plan = decode_plan(infos, reserve=len(files) * JPEG_DESC.itemsize)   # the table rows lead the JPEG upload
-        jtotal, planes = plan.upload_bytes, plan.plane_total
-        slot.reserve(total, nrows, self.device)
-        slot.reserve_jpeg(jtotal, jtotal + planes, self.device)
-        staged = torch.empty(total, dtype=torch.uint8, device=self.device) if ds.cache_images else slot.staged
-        host, jhost = slot.pinned.numpy(), slot.jpinned.numpy()
-
-        def work(k):
-            """True: file k's coefficients are in the JPEG staging; False: its PIL decode is in the image staging."""
-            (i, f), (blob, info) = files[k], probed[k]
-            if info is not None:
-                if blob is None:
-                    with open(f, 'rb') as fh:
-                        blob = fh.read()
-                if entropy_staged(blob, info, jhost, plan, k):
-                    return True
-            im = decode_image(f)
-            w0, h0 = (int(v) for v in ds.shapes_rgb[i])
-            if im.shape != (h0, w0, 3):
-                raise ValueError(f'{f}: decoded to {im.shape[1]}x{im.shape[0]}, scanned as {w0}x{h0}')
-            host[offs[k]:offs[k] + im.nbytes] = im.reshape(-1)
-            return False
-
-        on_device = list(pool.map(work, range(len(files))))
-        live = [k for k, d in enumerate(on_device) if d]
-        by_pil = [k for k, d in enumerate(on_device) if not d]
-        if by_pil:
-            lo = offs[by_pil[0]]
-            w0, h0 = (int(v) for v in ds.shapes_rgb[files[by_pil[-1]][0]])
-            hi = offs[by_pil[-1]] + h0 * w0 * 3
-            staged[lo:hi].copy_(slot.pinned[lo:hi], non_blocking=True)
-        if live:
-            table = np.zeros(len(live), dtype=JPEG_DESC)
-            fill_decode_rows(table, plan, infos, live, slot.jstaged.data_ptr(), [(staged.data_ptr() + offs[k], 3 * int(infos[k]["width"])) for k in live])
-            nb = len(live) * JPEG_DESC.itemsize
-            jhost[:nb] = table.view(np.uint8).reshape(-1)
-            slot.jstaged[:jtotal].copy_(slot.jpinned[:jtotal], non_blocking=True)
-            jpeg_decode_u8(slot.jstaged[:nb], slot.jpinned[:nb], len(live), slot.jstaged[jtotal:jtotal + planes])
+        entries = [(files[i], ds.original_size(i)) for i in missing for files in (ds.img_files_rgb, ds.img_files_ir)]
+        staged, views, _ = _upload(entries, nrows, slot, pool, self.device, ds.decode, ds.jpeg_infos, own_buffer=ds.cache_images)
         for n, i in enumerate(missing):
-            w0, h0 = (int(v) for v in ds.shapes_rgb[i])
-            by_index[i] = tuple(staged[offs[2 * n + s]:offs[2 * n + s] + h0 * w0 * 3].view(h0, w0, 3) for s in (0, 1))
+            by_index[i] = views[2 * n], views[2 * n + 1]
             if ds.cache_images:
                 ds.imgs_rgb[i], ds.imgs_ir[i] = by_index[i]
         return staged, by_index
 
     def _stage(self, b, slot, pool):
-        """Decode and upload batch ``b`` (side stream); returns what ``_assemble`` needs."""
+        """Decode and upload batch ``b`` (side stream); returns the upload's buffer and what ``_assemble`` needs."""
         ds, indices = self.dataset, self.batch_indices(b)
         try:
             desc, HW = ds.build_descriptors(indices)
         except LetterboxResizes:                         # assembled pair by pair (assemble_batch_by_pair): only the sizes are checked here
             desc, HW = np.zeros(len(indices), dtype=PAIR_DESC), None
             for row, index in zip(desc, indices):
-                row["h0"], row["w0"] = ds.pair_geometry(index)[:2]
-        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
-            # Whatever this does to the slot - the table always, the staging buffer when it is reused - comes after the launch that read
-            # the slot two batches ago: the consumer stream may be many batches behind the host.
-            if slot.consumed is not None:
-                self._side.wait_event(slot.consumed)
-            staged, by_index = self._upload(indices, len(indices), slot, pool)
-            sources = [by_index[i] for i in indices]
-            _fill_sources(desc, sources)
-            slot.desc_host[:len(indices)].numpy()[:] = desc.view(np.uint8).reshape(len(indices), -1)
-            slot.desc_dev[:len(indices)].copy_(slot.desc_host[:len(indices)], non_blocking=True)
-            slot.ready = torch.cuda.Event()
-            slot.ready.record(self._side)
-        return indices, HW, staged, sources
+                _fill_geometry(row, *ds.pair_geometry(index)[:7], flip=0)
+        staged, by_index = self._originals(indices, len(indices), slot, pool)
+        sources = [by_index[i] for i in indices]
+        _fill_sources(desc, sources)
+        slot.upload_table(len(indices), desc)
+        return staged, (indices, HW, sources)
 
-    def _assemble(self, slot, indices, HW, staged, sources):
+    def _assemble(self, slot, item):
         from ..ops import pair_batch_u8
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(slot.ready)
+        indices, HW, sources = item
         if HW is None:                                   # the letterbox resizes again: the per-image path
-            out = assemble_batch_by_pair(self.dataset, indices, sources)
-        else:
-            out = torch.empty((len(indices), 6, HW[0], HW[1]), dtype=torch.uint8, device=self.device)
-            pair_batch_u8(slot.desc_dev[:len(indices)], slot.desc_host[:len(indices)], out, 114)
-        slot.consumed = torch.cuda.Event()
-        slot.consumed.record(cur)
-        slot.desc_dev.record_stream(cur)                 # allocated on the side stream, read on this one
-        if staged is not None:
-            staged.record_stream(cur)
+            return assemble_batch_by_pair(self.dataset, indices, sources)
+        out = torch.empty((len(indices), 6, HW[0], HW[1]), dtype=torch.uint8, device=self.device)
+        pair_batch_u8(slot.desc_dev[:len(indices)], slot.desc_host[:len(indices)], out, 114)
         return out
 
     def __iter__(self):
-        from concurrent.futures import ThreadPoolExecutor
-        if self._side is None:
-            self._side = torch.cuda.Stream(self.device)
-        batches = list(self.batch_range)
-        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
-            nxt = stager.submit(self._stage, batches[0], self._slots[0], pool) if batches else None
-            for k, b in enumerate(batches):
-                staged = nxt.result()
-                slot = self._slots[k % 2]
-                # the next batch decodes and uploads while this one is assembled and used
-                nxt = stager.submit(self._stage, batches[k + 1], self._slots[(k + 1) % 2], pool) if k + 1 < len(batches) else None
-                img = self._assemble(slot, *staged)
-                targets, paths, shapes = self.dataset.batch_targets(staged[0])
-                yield img, targets, paths, shapes
+        for (indices, _, _), img in self._pipe.run(self.batch_range, self._stage, self._assemble):
+            yield (img, *self.dataset.batch_targets(indices))
 
 
 def _align16(n):
@@ -789,23 +865,15 @@ class LoadMultiModalImagesAndLabelsAugmented(LoadMultiModalImagesAndLabels):
     def _check_sizes(self, prefix=''):
         """load_image_rgb_ir resizes with INTER_LINEAR in both directions when augmenting: any ratio up to the kernel's size limit."""
         limit = _lib._consts["CFT_AUG_MAX_SIDE"]
-        for f, (w0, h0) in zip(self.img_files_rgb, self.shapes_rgb.astype(int)):
+        for index, f in enumerate(self.img_files_rgb):
+            h0, w0 = self.original_size(index)
             if max(h0, w0, 2 * self.img_size) > limit or min(self.resized_size(h0, w0)) < 1:
                 raise ValueError(f'{prefix}{f} is {w0}x{h0}: img_size={self.img_size} is outside what cft_augment_batch_u8 takes (sides of 1..{limit})')
-
-    def resized_size(self, h0, w0):
-        """(h, w) of load_image_rgb_ir (:1361-1367)."""
-        r = self.img_size / max(h0, w0)  # ratio
-        return (int(h0 * r), int(w0 * r)) if r != 1 else (h0, w0)
 
     def letterbox_geometry_aug(self, index):
         """The non-mosaic branch's geometry (:1202-1209, letterbox(auto=False, scaleup=True)):
         ``(h0, w0, h, w, top, left, (H, W), ratio, pad, new_unpad)``."""
-        w0, h0 = (int(v) for v in self.shapes_rgb[index])
-        h, w = self.resized_size(h0, w0)
-        shape = self.batch_shapes_rgb[self.batch_rgb[index]] if self.rect else self.img_size  # final letterboxed shape
-        new_unpad, ratio, pad, (top, bottom, left, right) = letterbox_geometry((h, w), shape, auto=False, scaleup=True)
-        return h0, w0, h, w, top, left, (new_unpad[1] + top + bottom, new_unpad[0] + left + right), ratio, pad, new_unpad
+        return self._letterbox(index, scaleup=True)
 
     def item_plan(self, index, rng, np_rng):
         """Everything item ``index`` needs, drawing from ``rng`` (random.Random) and ``np_rng`` (numpy.random.RandomState) in exactly
@@ -822,7 +890,7 @@ class LoadMultiModalImagesAndLabelsAugmented(LoadMultiModalImagesAndLabels):
             indices = [index] + rng.choices(self.indices_rgb, k=3)  # 3 additional image indices
             tiles, labels4 = [], []
             for i, k in enumerate(indices):
-                w0, h0 = (int(v) for v in self.shapes_rgb[k])
+                h0, w0 = self.original_size(k)
                 h, w = self.resized_size(h0, w0)
                 x1, y1, x2, y2, padw, padh = mosaic_tile_rects(i, xc, yc, w, h, s)
                 tiles.append({"index": k, "h0": h0, "w0": w0, "h": h, "w": w, "x1": x1, "y1": y1, "x2": x2, "y2": y2, "padw": padw, "padh": padh})
@@ -837,29 +905,14 @@ class LoadMultiModalImagesAndLabelsAugmented(LoadMultiModalImagesAndLabels):
         else:
             h0, w0, h, w, top, left, (H, W), ratio, pad, new_unpad = self.letterbox_geometry_aug(index)
             assert new_unpad == (w, h), f"pair {index}: the letterbox would resize {w}x{h} again"
-            plan.update(indices=[index], canvas=(H, W), out=(H, W), shapes=((h0, w0), ((h / h0, w / w0), pad)),
+            labels, shapes = self._letterboxed_labels(index, h0, w0, h, w, ratio, pad)
+            plan.update(indices=[index], canvas=(H, W), out=(H, W), shapes=shapes,
                         tiles=[{"index": index, "h0": h0, "w0": w0, "h": h, "w": w, "x1": left, "y1": top, "x2": left + w, "y2": top + h, "padw": left, "padh": top}])
-            labels = self.labels_rgb[index].copy()
-            if labels.size:  # normalized xywh to pixel xyxy format
-                labels[:, 1:] = xywhn2xyxy(labels[:, 1:], ratio[0] * w, ratio[1] * h, padw=pad[0], padh=pad[1])
         # Augment colorspace: one draw of three per stream, RGB first
         gains = [np_rng.uniform(-1, 1, 3) * [hyp['hsv_h'], hyp['hsv_s'], hyp['hsv_v']] + 1 for _ in range(2)]
-        H, W = plan["out"]
-        nL = len(labels)  # number of labels
-        if nL:
-            labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])  # convert xyxy to xywh
-            labels[:, [2, 4]] /= H  # normalized height 0-1
-            labels[:, [1, 3]] /= W  # normalized width 0-1
         flipud = rng.random() < hyp['flipud']
-        if flipud and nL:
-            labels[:, 2] = 1 - labels[:, 2]
         fliplr = rng.random() < hyp['fliplr']
-        if fliplr and nL:
-            labels[:, 1] = 1 - labels[:, 1]
-        labels_out = torch.zeros((nL, 6))
-        if nL:
-            labels_out[:, 1:] = torch.from_numpy(labels)
-        plan.update(gains=gains, flipud=bool(flipud), fliplr=bool(fliplr), labels_out=labels_out)
+        plan.update(gains=gains, flipud=bool(flipud), fliplr=bool(fliplr), labels_out=_labels_out(labels, *plan["out"], flipud, fliplr))
         return plan
 
     def _random_affine(self, targets, rng, canvas, border):
@@ -903,10 +956,7 @@ class LoadMultiModalImagesAndLabelsAugmented(LoadMultiModalImagesAndLabels):
 
     def plan_targets(self, plans):
         """``(targets [nt, 6] float32 CPU, paths, shapes)`` of one planned batch: the reference's ``collate_fn`` (:1284-1288)."""
-        label = [p["labels_out"].clone() for p in plans]
-        for i, l in enumerate(label):
-            l[:, 0] = i  # add target image index for build_targets()
-        return torch.cat(label, 0), tuple(self.img_files_rgb[p["index"]] for p in plans), tuple(p["shapes"] for p in plans)
+        return self._collate([p["labels_out"].clone() for p in plans], [p["index"] for p in plans], [p["shapes"] for p in plans])
 
 
 def build_augment_descriptors(plans):
@@ -935,23 +985,14 @@ def _fill_aug_sources(table, plans, by_index):
     """Source pointers and strides of every tile from ``by_index``: {pair index: (rgb, ir) HWC RGB uint8 CUDA tensors}."""
     for row, p in zip(table, plans):
         for tile, t in zip(row["tile"], p["tiles"]):
-            rgb, ir = by_index[t["index"]]
-            for x in (rgb, ir):
-                if x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3 or x.stride(2) != 1 or x.stride(1) != 3 or not x.is_cuda:
-                    raise ValueError("pair sources must be HWC uint8 CUDA tensors with contiguous pixels")
-                if tuple(x.shape[:2]) != (t["h0"], t["w0"]):
-                    raise ValueError(f"pair source is {tuple(x.shape[:2])}, the table says {(t['h0'], t['w0'])}")
-            tile["src_rgb"], tile["src_ir"], tile["stride_rgb"], tile["stride_ir"] = rgb.data_ptr(), ir.data_ptr(), rgb.stride(0), ir.stride(0)
+            _fill_source(tile, *by_index[t["index"]], t["h0"], t["w0"])
 
 
 def augment_batch(table, luts, out):
     """Launch cft_augment_batch_u8: ``table`` a filled AUG_DESC array and ``luts`` uint8 [B, 2, 3, 256] (host), ``out`` the uint8 CUDA
     [B, 6, H, W] batch to write.  The device copies are made on the current stream from pinned memory."""
     from ..ops import augment_batch_u8
-    host = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(len(table), -1)).pin_memory()
-    luts_host = torch.from_numpy(np.ascontiguousarray(luts)).pin_memory()
-    augment_batch_u8(host.to(out.device, non_blocking=True), host, luts_host.to(out.device, non_blocking=True), out)
-    return out
+    return _launch_direct(augment_batch_u8, out, table, luts)
 
 
 def assemble_augmented_batch(dataset, indices, device, rng, np_rng, sources=None, return_plans=False):
@@ -988,17 +1029,17 @@ def batch_generators(seed, epoch, batch):
 
 class AugmentedPairLoader(PairLoader):
     """The iterable ``create_train_dataloader_rgb_ir`` returns: yields ``(img6 uint8 cuda [B, 6, H, W], targets float32 CPU [nt, 6],
-    paths, shapes)`` per batch in dataset order (the reference's loader does not shuffle).  Decode pool, the two staging slots and the
-    side stream are ``PairLoader``'s; a batch's up-to-4B distinct pairs are decoded once each, and with ``cache_images`` only the
-    table and the look-up tables are uploaded once the originals are on the device.  The next batch is planned on the stager thread,
-    so the global ``random`` / ``np.random`` are never touched: batch ``b`` of epoch ``e`` draws from ``batch_generators(seed, e, b)``.
-    ``set_epoch(e)`` sets the epoch of the next pass; otherwise every ``__iter__`` advances it."""
+    paths, shapes)`` per batch in dataset order (the reference's loader does not shuffle).  Batches come through the same prefetch
+    pipeline as ``PairLoader``'s (``_Prefetch``); a batch's up-to-4B distinct pairs are decoded once each, and with ``cache_images``
+    only the table and the look-up tables are uploaded once the originals are on the device.  The next batch is planned on the stager
+    thread, so the global ``random`` / ``np.random`` are never touched: batch ``b`` of epoch ``e`` draws from
+    ``batch_generators(seed, e, b)``.  ``set_epoch(e)`` sets the epoch of the next pass; otherwise every ``__iter__`` advances it."""
+    ROW_BYTES = AUG_DESC.itemsize + AUG_LUT_BYTES
 
     def __init__(self, dataset, batch_size, workers=8, rank=-1, world_size=1, device=None, seed=0):
         super().__init__(dataset, batch_size, workers=workers, rank=rank, world_size=world_size, device=device)
         self.seed = int(seed)
         self.epoch = 0
-        self._slots = (_Slot(AUG_DESC.itemsize + AUG_LUT_BYTES), _Slot(AUG_DESC.itemsize + AUG_LUT_BYTES))
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -1009,54 +1050,27 @@ class AugmentedPairLoader(PairLoader):
         return [self.dataset.item_plan(i, rng, np_rng) for i in self.batch_indices(b)]
 
     def _stage(self, b, slot, pool, epoch):
-        """Plan, decode and upload batch ``b`` (side stream); returns what ``_assemble`` needs."""
+        """Plan, decode and upload batch ``b`` (side stream); returns the upload's buffer and what ``_assemble`` needs."""
         plans = self.plan_batch(b, epoch)
-        n = len(plans)
         table, luts, HW = build_augment_descriptors(plans)
-        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
-            if slot.consumed is not None:                # after the launch that read this slot two batches ago
-                self._side.wait_event(slot.consumed)
-            staged, by_index = self._upload(sorted({t["index"] for p in plans for t in p["tiles"]}), n, slot, pool)
-            _fill_aug_sources(table, plans, by_index)
-            host = slot.desc_host[:n].view(-1).numpy()   # the table, then the look-up tables, in one upload
-            host[:n * AUG_DESC.itemsize] = table.view(np.uint8).reshape(-1)
-            host[n * AUG_DESC.itemsize:] = luts.reshape(-1)
-            slot.desc_dev[:n].copy_(slot.desc_host[:n], non_blocking=True)
-            slot.ready = torch.cuda.Event()
-            slot.ready.record(self._side)
-        return plans, HW, staged, by_index
+        staged, by_index = self._originals(sorted({t["index"] for p in plans for t in p["tiles"]}), len(plans), slot, pool)
+        _fill_aug_sources(table, plans, by_index)
+        slot.upload_table(len(plans), table, luts)       # the table, then the look-up tables, in one upload
+        return staged, (plans, HW)
 
-    def _assemble(self, slot, plans, HW, staged, by_index):
+    def _assemble(self, slot, item):
         from ..ops import augment_batch_u8
+        plans, HW = item
         n, nb = len(plans), len(plans) * AUG_DESC.itemsize
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(slot.ready)
         out = torch.empty((n, 6, HW[0], HW[1]), dtype=torch.uint8, device=self.device)
         dev, host = slot.desc_dev[:n].view(-1), slot.desc_host[:n].view(-1)
         augment_batch_u8(dev[:nb].view(n, -1), host[:nb].view(n, -1), dev[nb:].view(n, 2, 3, 256), out)
-        slot.consumed = torch.cuda.Event()
-        slot.consumed.record(cur)
-        slot.desc_dev.record_stream(cur)                 # allocated on the side stream, read on this one
-        if staged is not None:
-            staged.record_stream(cur)
         return out
 
     def __iter__(self):
-        from concurrent.futures import ThreadPoolExecutor
-        if self._side is None:
-            self._side = torch.cuda.Stream(self.device)
         epoch, self.epoch = self.epoch, self.epoch + 1
-        batches = list(self.batch_range)
-        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
-            nxt = stager.submit(self._stage, batches[0], self._slots[0], pool, epoch) if batches else None
-            for k, b in enumerate(batches):
-                staged = nxt.result()
-                slot = self._slots[k % 2]
-                # the next batch is planned, decoded and uploaded while this one is assembled and used
-                nxt = stager.submit(self._stage, batches[k + 1], self._slots[(k + 1) % 2], pool, epoch) if k + 1 < len(batches) else None
-                img = self._assemble(slot, *staged)
-                targets, paths, shapes = self.dataset.plan_targets(staged[0])
-                yield img, targets, paths, shapes
+        for (plans, _), img in self._pipe.run(self.batch_range, lambda b, slot, pool: self._stage(b, slot, pool, epoch), self._assemble):
+            yield (img, *self.dataset.plan_targets(plans))
 
 
 def create_train_dataloader_rgb_ir(path1, path2, imgsz, batch_size, stride, opt, hyp, cache=False, rect=False, rank=-1, world_size=1,
@@ -1151,10 +1165,11 @@ def image_size(path):
 class LoadImagePairs:
     """Two ``LoadImages`` lists zipped as detect_twostream.py:66 zips them, in batches: consecutive pairs of the same original size
     (up to ``batch_size``) form one uint8 ``[B, 6, H, W]`` batch.  Iterating yields ``(paths, img6, originals, shapes)``: ``paths`` a list
-    of (rgb path, ir path), ``originals`` a list of (rgb, ir) HWC RGB uint8 CUDA tensors (kept for drawing and cropping), ``shapes`` a list
-    of ``((h0, w0), None)`` as ``utils.metrics.geometry`` takes them; ``host_originals`` holds the decoded arrays of the batch just yielded.  A batch is one cft_pair_batch_u8 launch (CFT_PAIR_LINEAR, or
+    of (rgb path, ir path), ``originals`` a list of (rgb, ir) HWC RGB uint8 CUDA tensors (kept for drawing and cropping: they live in a
+    device buffer of their batch's own), ``shapes`` a list of ``((h0, w0), None)`` as ``utils.metrics.geometry`` takes them;
+    ``host_originals`` holds the decoded arrays of the batch just yielded.  A batch is one cft_pair_batch_u8 launch (CFT_PAIR_LINEAR, or
     CFT_PAIR_COPY at ratio 1) where that kernel's guards admit it - an enlarging letterbox - else two cft_letterbox_u8 launches per pair.
-    The next batch is decoded on at most 16 threads and uploaded on a side stream while the current one is in use."""
+    Batches come through the prefetch pipeline of the paired loaders (``_Prefetch``), decoded by PIL on at most 16 threads."""
 
     def __init__(self, source1, source2, img_size=640, stride=32, batch_size=1, workers=8, device=None):
         self.rgb = LoadImages(source1, img_size, stride)
@@ -1177,7 +1192,7 @@ class LoadImagePairs:
                 self.batches[-1].append(i)
             else:
                 self.batches.append([i])
-        self._side = None
+        self._pipe = _Prefetch(self.device, self.workers)
         self.host_originals = None
 
     def __len__(self):
@@ -1196,65 +1211,34 @@ class LoadImagePairs:
             return PAIR_LINEAR, g
         return None, g
 
-    def _load(self, i):
-        rgb, ir = decode_image(self.pairs[i][0]), decode_image(self.pairs[i][1])
-        for im, f in zip((rgb, ir), self.pairs[i]):
-            if im.shape[:2] != self.shapes[i]:
-                raise ValueError(f'{f}: decoded to {im.shape[1]}x{im.shape[0]}, its header says {self.shapes[i][1]}x{self.shapes[i][0]}')
-        return rgb, ir
-
-    def _stage(self, indices, pool):
-        """Decode and upload one batch on the side stream: (originals, device table or None, host table, event)."""
-        decoded = list(pool.map(self._load, indices))
-        nbytes = _align16(decoded[0][0].nbytes)
+    def _stage(self, indices, slot, pool):
+        """Decode and upload one batch (side stream), with its table where one launch assembles it."""
+        entries = [(f, self.shapes[i]) for i in indices for f in self.pairs[i]]
+        staged, views, decoded = _upload(entries, len(indices), slot, pool, self.device, own_buffer=True)   # the originals outlive the batch
+        originals = list(zip(views[0::2], views[1::2]))
         mode, (H, W, rh, rw, top, left) = self.batch_mode(indices)
-        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
-            pinned = torch.empty(2 * nbytes * len(indices), dtype=torch.uint8).pin_memory()
-            host = pinned.numpy()
-            for k, (rgb, ir) in enumerate(decoded):
-                host[2 * k * nbytes:2 * k * nbytes + rgb.nbytes] = rgb.reshape(-1)
-                host[(2 * k + 1) * nbytes:(2 * k + 1) * nbytes + ir.nbytes] = ir.reshape(-1)
-            staged = pinned.to(self.device, non_blocking=True)
-            h0, w0 = self.shapes[indices[0]]
-            originals = [tuple(staged[(2 * k + s) * nbytes:(2 * k + s) * nbytes + h0 * w0 * 3].view(h0, w0, 3) for s in (0, 1))
-                         for k in range(len(indices))]
-            desc_host = desc_dev = None
-            if mode is not None:
-                desc = np.zeros(len(indices), dtype=PAIR_DESC)
-                for row in desc:
-                    row["h0"], row["w0"], row["h"], row["w"], row["top"], row["left"], row["mode"], row["flip"] = h0, w0, rh, rw, top, left, mode, 0
-                _fill_sources(desc, originals)
-                desc_host = torch.from_numpy(desc.view(np.uint8).reshape(len(indices), -1)).pin_memory()
-                desc_dev = desc_host.to(self.device, non_blocking=True)
-            ready = torch.cuda.Event()
-            ready.record(self._side)
-        return indices, originals, staged, desc_host, desc_dev, ready, decoded
+        if mode is not None:
+            desc = np.zeros(len(indices), dtype=PAIR_DESC)
+            for row in desc:
+                _fill_geometry(row, *self.shapes[indices[0]], rh, rw, top, left, mode, flip=0)
+            _fill_sources(desc, originals)
+            slot.upload_table(len(indices), desc)
+        return staged, (indices, originals, list(zip(decoded[0::2], decoded[1::2])))
 
-    def _assemble(self, indices, originals, staged, desc_host, desc_dev, ready, decoded):
+    def _assemble(self, slot, item):
         from ..ops import pair_batch_u8
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(ready)
-        staged.record_stream(cur)                            # allocated on the side stream, read on this one
-        _, (H, W, rh, rw, top, left) = self.batch_mode(indices)
+        indices, originals, _ = item
+        mode, (H, W, rh, rw, top, left) = self.batch_mode(indices)
         out = torch.empty((len(indices), 6, H, W), dtype=torch.uint8, device=self.device)
-        if desc_dev is not None:
-            desc_dev.record_stream(cur)
-            pair_batch_u8(desc_dev, desc_host, out, 114)
+        if mode is not None:
+            pair_batch_u8(slot.desc_dev[:len(indices)], slot.desc_host[:len(indices)], out, 114)
         else:
             for k, (rgb, ir) in enumerate(originals):
                 _letterbox_chw_rgb(rgb, out[k, :3], rh, rw, top, left)
                 _letterbox_chw_rgb(ir, out[k, 3:], rh, rw, top, left)
-        self.host_originals = decoded                        # the same pixels on the host, (rgb, ir) numpy arrays of the batch just yielded
-        paths = [self.pairs[i] for i in indices]
-        return paths, out, originals, [(self.shapes[i], None) for i in indices]
+        return out
 
     def __iter__(self):
-        from concurrent.futures import ThreadPoolExecutor
-        if self._side is None:
-            self._side = torch.cuda.Stream(self.device)
-        with ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as stager:
-            nxt = stager.submit(self._stage, self.batches[0], pool) if self.batches else None
-            for k in range(len(self.batches)):
-                staged = nxt.result()
-                nxt = stager.submit(self._stage, self.batches[k + 1], pool) if k + 1 < len(self.batches) else None
-                yield self._assemble(*staged)
+        for (indices, originals, decoded), out in self._pipe.run(self.batches, self._stage, self._assemble):
+            self.host_originals = decoded                    # the same pixels on the host, (rgb, ir) numpy arrays of the batch just yielded
+            yield [self.pairs[i] for i in indices], out, originals, [(self.shapes[i], None) for i in indices]

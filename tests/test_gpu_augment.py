@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import augment_ref as AR
+from gpu_busy import busy
 
 pytestmark = pytest.mark.gpu
 
@@ -268,6 +269,31 @@ def test_epochs_advance_on_their_own_and_ranks_take_their_shard(dev):
         assert list(shard.batch_range) == list(range(*shard_bounds(2, rank, 2)))
         got = [img.cpu() for img, *_ in shard]
         assert len(got) == len(shard) and all(torch.equal(g, first[b]) for g, b in zip(got, shard.batch_range))     # whichever rank assembles it
+
+
+@pytest.mark.parametrize("cache", [False, "device"], ids=["uncached", "cached"])
+def test_augmented_loader_reuses_a_slot_only_after_the_launch_that_read_it(dev, cache):
+    """test_gpu_dataset.py's test of the same name, for this loader: one item per batch, slow work queued on the consumer stream before
+    every launch, so the slot's table and look-up tables are rewritten for batch k + 2 while batch k's launch is still queued - in the
+    pass that fills the device cache and in the one that reads it.  Every batch must still be its own."""
+    from msod_amd.utils import datasets as D
+    loader, ds = _loader(dict(B64, batch_size=1), cache=cache)
+    assert len(loader) == len(ds) > 2
+    torch.cuda.synchronize()
+    for epoch in (0, 1):
+        got, tail = [], None
+        busy(dev)
+        for img, _, _, _ in loader:
+            got.append(img.clone())
+            tail = busy(dev)
+        pending = not torch.cuda.current_stream().query()                  # the host got here with consumer work still queued
+        torch.cuda.synchronize()
+        print(f"epoch {epoch}: consumer stream still busy when the host finished: {pending}")
+        assert len(got) == len(loader) and tail is not None
+        for b, g in enumerate(got):
+            want = D.assemble_augmented_batch(ds, loader.batch_indices(b), dev, *D.batch_generators(5, epoch, b))
+            assert torch.equal(g, want), f"epoch {epoch}: batch {b}"
+    assert all((t is not None) == bool(cache) for t in ds.imgs_rgb)
 
 
 # ------------------------------------------------------------------------------ closed loop

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import dataset_ref as DR
+from gpu_busy import busy as _busy
 from oracle import letterbox_oracle as LO
 
 pytestmark = pytest.mark.gpu
@@ -187,17 +188,6 @@ def test_loader_end_to_end(dev, c):
             assert img.is_cuda and img.dtype == torch.uint8 and torch.equal(img, direct)
             assert targets.device.type == "cpu" and torch.equal(targets, want["targets"])
             assert [os.path.relpath(p, ROOT) for p in paths] == want["paths"] and DR.plain(shapes) == want["shapes"]
-
-
-def _busy(dev, state={}):
-    """Queue some tens of milliseconds of work on the current stream, so that what is launched next is still waiting while the host
-    goes on (a chain of 4096 x 4096 fp32 products, 137 GFLOP each)."""
-    if "a" not in state:
-        state["a"] = torch.randn((4096, 4096), device=dev) / 64
-    x = state["a"]
-    for _ in range(12):
-        x = x @ state["a"]
-    return x
 
 
 def test_loader_reuses_a_slot_only_after_the_launch_that_read_it(dev):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import detect_ref
+from gpu_busy import busy
 
 pytestmark = pytest.mark.gpu
 
@@ -86,6 +87,34 @@ def test_load_image_pairs_batches_equal_letterbox_pair(dev, folders):
     ones, fours = load(1), load(4)
     assert [t.shape[0] for t in ones] == [1] * 6 and [t.shape[0] for t in fours] == [3, 2, 1]
     assert torch.equal(torch.cat(ones[:3]), fours[0]) and torch.equal(torch.cat(ones[3:5]), fours[1]) and torch.equal(ones[5], fours[2])
+
+
+def test_load_image_pairs_reuses_a_slot_only_after_the_launch_that_read_it(dev, folders):
+    """test_gpu_dataset.py's test of the same name, for this loader: one pair per batch, so consecutive batches differ in size and
+    reuse the two slots; slow work is queued on the consumer stream before every batch and the loop body waits for nothing.  Every
+    batch must still be its own, and - the slots being reused - every earlier batch's originals must still be its files afterwards."""
+    import msod_amd  # noqa: F401
+    from msod_amd.utils import datasets as D
+    rgb, ir = _decoded(folders, "rgb"), _decoded(folders, "ir")
+    ds = D.LoadImagePairs(str(folders / "rgb"), str(folders / "ir"), IMG_SIZE, 32, batch_size=1, device=dev)
+    assert ds.batches == [[i] for i in range(6)]
+    want = [D.letterbox_pair(torch.from_numpy(np.ascontiguousarray(rgb[i][:, :, ::-1])).to(dev),
+                             torch.from_numpy(np.ascontiguousarray(ir[i][:, :, ::-1])).to(dev), IMG_SIZE, stride=32, auto=True, scaleup=True)[0] for i in range(6)]
+    torch.cuda.synchronize()
+    for what in ("first pass", "second pass"):
+        kept, tail = [], None
+        busy(dev)
+        for paths, img6, originals, shapes in ds:
+            kept.append((img6.clone(), originals))
+            tail = busy(dev)
+        pending = not torch.cuda.current_stream().query()                  # the host got here with consumer work still queued
+        torch.cuda.synchronize()
+        print(f"{what}: consumer stream still busy when the host finished: {pending}")
+        assert len(kept) == 6 and tail is not None
+        for i, (img6, originals) in enumerate(kept):
+            assert tuple(img6.shape[1:]) == tuple(want[i].shape) and torch.equal(img6[0], want[i]), f"{what}: batch {i}"
+            (o_rgb, o_ir), = originals
+            assert np.array_equal(o_rgb.cpu().numpy(), rgb[i]) and np.array_equal(o_ir.cpu().numpy(), ir[i]), f"{what}: originals of batch {i}"
 
 
 def test_load_images_on_the_gpu(dev, folders):

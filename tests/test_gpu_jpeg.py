@@ -163,10 +163,11 @@ def test_loader_with_device_decode_equals_pil(dev, jpeg_tree):
             assert np.array_equal(t.cpu().numpy(), D.decode_image(f))
 
 
-def test_mixed_folder_is_judged_per_file(dev, jpeg_tree, tmp_path):
+@pytest.fixture(scope="module")
+def mixed_tree(jpeg_tree, tmp_path_factory):
     """Among the JPEG pairs: one PNG pair, one progressive RGB JPEG, one RGB-JPEG / IR-PNG pair."""
     from PIL import Image
-    root = tmp_path / "mixed"
+    root = tmp_path_factory.mktemp("mixed_pairs") / "mixed"
     shutil.copytree(jpeg_tree, root)
     names = sorted(n[:-4] for n in os.listdir(root / "rgb" / "images"))
     png_pair, progressive, half = names[0], names[1], names[2]
@@ -177,6 +178,11 @@ def test_mixed_folder_is_judged_per_file(dev, jpeg_tree, tmp_path):
         im.convert("RGB").save(root / "rgb" / "images" / (progressive + ".jpg"), quality=90, progressive=True)
     os.remove(root / "ir" / "images" / (half + ".jpg"))
     shutil.copy(os.path.join(ROOT, "ir", "images", half + ".png"), root / "ir" / "images" / (half + ".png"))
+    return root
+
+
+def test_mixed_folder_is_judged_per_file(dev, mixed_tree):
+    root = mixed_tree
     (want,), ds0 = _passes(root, False)
     assert {os.path.splitext(f)[1] for f in ds0.img_files_rgb + ds0.img_files_ir} == {".jpg", ".png"}
     with counting_device_decodes() as seen:
@@ -186,6 +192,51 @@ def test_mixed_folder_is_judged_per_file(dev, jpeg_tree, tmp_path):
     (first, second), _ = _passes(root, True, cache='device', n=2)
     _assert_same_batches(first, want)
     _assert_same_batches(second, want)
+
+
+def test_mixed_folder_with_cache_images_opens_no_file_in_the_second_pass(dev, mixed_tree, monkeypatch):
+    """``cache_images=True`` over the mixed folder: JPEG and PNG files of one batch go through one upload into the batch's own buffer,
+    and once every original is cached a pass neither decodes, probes nor launches the device decoder."""
+    from msod_amd.utils import datasets as D
+    (want,), _ = _passes(mixed_tree, False)
+    loader, ds = quiet(D.create_dataloader_rgb_ir, str(mixed_tree / "rgb" / "images"), str(mixed_tree / "ir" / "images"), 64, 4, 32, OPT, rect=True,
+                       pad=0.5, workers=4, cache=True)
+    D.use_device_jpeg(loader)
+    with counting_device_decodes() as seen:
+        first = [(img.clone(), t, p, s) for img, t, p, s in loader]
+    assert seen == [len(want), 2 * len(ds) - 4] and all(t is not None and t.is_cuda for t in ds.imgs_rgb + ds.imgs_ir)
+
+    def refuse(*a, **k):
+        raise AssertionError("a pass over cached originals opened a file")
+    monkeypatch.setattr(D, "decode_image", refuse)
+    monkeypatch.setattr(D, "_probe_jpeg", refuse)
+    monkeypatch.setattr(ds, "load_pair", refuse)
+    with counting_device_decodes() as seen:
+        second = [(img.clone(), t, p, s) for img, t, p, s in loader]
+    assert seen == [0, 0]
+    _assert_same_batches(first, want)
+    _assert_same_batches(second, want)
+
+
+def test_a_pass_without_device_jpegs_reserves_no_jpeg_staging(dev):
+    """``decode='pil'`` over the PNG fixture: one pass leaves the JPEG staging of both slots unallocated and launches no device decode;
+    nor does ``decode='device'`` there, where every file is judged and none qualifies."""
+    from msod_amd.utils import datasets as D
+    loader, ds = quiet(D.create_dataloader_rgb_ir, os.path.join(ROOT, "rgb", "images"), os.path.join(ROOT, "ir", "images"), 64, 4, 32, OPT, rect=True,
+                       pad=0.5, workers=4)
+    assert ds.decode == 'pil' and len(loader) >= 2                 # both slots are used
+    want = None
+    for decode in ('pil', 'device'):
+        D.use_device_jpeg(loader, enabled=decode == 'device')
+        with counting_device_decodes() as seen:
+            got = [(img.clone(), t, p, s) for img, t, p, s in loader]
+        assert seen == [0, 0]
+        slots = loader._pipe.slots
+        assert all(s.pinned is not None and s.staged is not None for s in slots), decode
+        assert all(s.jpinned is None and s.jstaged is None for s in slots), decode
+        want = want or got
+        _assert_same_batches(got, want)
+    assert set(ds.jpeg_infos.values()) == {None} and len(ds.jpeg_infos) == 2 * len(ds)
 
 
 def test_training_batch_is_the_same_with_both_decoders(dev, jpeg_tree):

@@ -27,6 +27,10 @@ from msod_amd.ops import pair_batch_u8  # noqa: E402
 from msod_amd.utils import datasets as D  # noqa: E402
 
 
+# the augmentation hyper-parameters of the reference's data/hyp.scratch.yaml
+AUGMENT_HYP = dict(mosaic=1.0, degrees=0.0, translate=0.1, scale=0.5, shear=0.0, perspective=0.0, hsv_h=0.015, hsv_s=0.7, hsv_v=0.4, flipud=0.0, fliplr=0.5)
+
+
 def timed(fn, runs, warmup=5):
     for _ in range(warmup):
         fn()
@@ -80,19 +84,28 @@ def loader_rate(B, dev, passes=2):
                 img = ((x * (k % 5 + 1) + y * (k % 3 + 1))[..., None] + g.randint(0, 32, (512, 640, 3))).astype(np.uint8)
                 Image.fromarray(img).save(os.path.join(root, stream, "images", f"{k:04d}.png"), compress_level=1)
         out = {}
-        for name, cache in (("uncached", False), ("device_cached", 'device')):
-            loader, ds = D.create_dataloader_rgb_ir(os.path.join(root, "rgb", "images"), os.path.join(root, "ir", "images"), 640, B, 32,
-                                                    SimpleNamespace(single_cls=False), pad=0.5, rect=True, cache=cache, workers=16)
+        rgb, ir, opt = os.path.join(root, "rgb", "images"), os.path.join(root, "ir", "images"), SimpleNamespace(single_cls=False)
+
+        def rate(key, loader, pairs):
             rates = []
             for _ in range(passes + 1):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                for img, _, _, _ in loader:
+                for _ in loader:
                     pass
                 torch.cuda.synchronize()
-                rates.append(len(ds) / (time.perf_counter() - t0))
-            out[name + "_pairs_per_s"] = round(statistics.median(rates[1:]), 1)       # the first pass warms up (and fills the cache)
-            out[name + "_first_pass_pairs_per_s"] = round(rates[0], 1)
+                rates.append(pairs / (time.perf_counter() - t0))
+            out[key + "_pairs_per_s"] = round(statistics.median(rates[1:]), 1)       # the first pass warms up (and fills the cache)
+            out[key + "_first_pass_pairs_per_s"] = round(rates[0], 1)
+
+        for name, cache in (("uncached", False), ("device_cached", 'device')):
+            loader, ds = D.create_dataloader_rgb_ir(rgb, ir, 640, B, 32, opt, pad=0.5, rect=True, cache=cache, workers=16)
+            rate(name, loader, len(ds))
+            # the training loader: mosaics of four pairs each (no labels in this tree), so a pass decodes most pairs several times uncached
+            loader, ds = D.create_train_dataloader_rgb_ir(rgb, ir, 640, B, 32, opt, AUGMENT_HYP, cache=cache, workers=16)
+            rate("augmented_" + name, loader, len(ds))
+        pairs = D.LoadImagePairs(rgb, ir, 640, 32, batch_size=B, workers=16, device=dev)
+        rate("detect", pairs, len(pairs.pairs))
     return out
 
 
