@@ -615,6 +615,37 @@ int cft_eval_ap(const unsigned short* tp_bits, const float* conf, const int* pcl
                 const double* px, const double* x, void* workspace, long workspace_bytes, double* out, void* stream);
 
 /*
+ * cft_eval_curves: the curves of a validation run over the same n accumulated detections, sorted as cft_eval_ap sorts them (the
+ * call sorts by itself: it needs no preceding cft_eval_ap and leaves that call's results alone).  All at IoU column 0 (bit 0 of
+ * tp_bits), float64, one row per class c in [0, nc); rows of classes with label_hist[c] <= 0 are zero.
+ *   pcurve, rcurve, f1curve [nc, 1000] : precision, recall and f1 = 2 p r / (p + r + 1e-16) at the px points, np.interp(-px, -conf, .)
+ *       with left = 1 / 0 (utils/metrics.py:57, :61, :70): what plot=True draws as P_curve, R_curve and F1_curve.
+ *   pycurve [nc, 1000] : np.interp(px, mrec, mpre) with compute_ap's arrays (:67, :93-97; sentinels 0 and recall[-1] + 0.01, 1 and
+ *       0, reverse running maximum): PR_curve.  A class with labels and no predictions has a row of zeros (the reference appends
+ *       no row for it).
+ *   best [1] int : the index of f1.mean(0).argmax() over the classes with labels (:77), first index on ties, a NaN wins; the index
+ *       at which cft_eval_ap reads its p, r and f1.
+ *   mr [nc, ng] : the miss rate at each value of fppi_grid.  With n_l = label_hist[c] and the class's predictions by descending
+ *       conf (ties in insertion order): tpc[k] = TPs among the first k + 1, fpc[k] = k + 1 - tpc[k], fppi[k] = fpc[k] / n_images,
+ *       miss[k] = 1 - tpc[k] / (n_l + 1e-16), preceded by the sentinel fppi = -1, miss = 1; mr[c, g] = miss at the LAST index with
+ *       fppi <= fppi_grid[g].  So a grid value below the first fppi gives 1, the last prediction holds up to +inf, and a class with
+ *       labels and no predictions has a row of ones.  Counts are exact integers; each value is one division and one subtraction.
+ *       This is the Caltech (Dollar et al.) false-positives-per-image / miss-rate curve on this evaluator's own matching; the
+ *       log-average miss rate is the geometric mean of mr at np.logspace(-2, 0, 9), taken on the host.
+ *   tp_bits, conf, pcls, n, label_hist, nc : as for cft_eval_ap;  n_images >= 1 : the images seen
+ *   px [1000] : np.linspace(0, 1, 1000) (device)
+ *   fppi_grid [ng] (device) and fppi_grid_host [ng] (the same values on the host, checked there): finite, non-decreasing,
+ *       1 <= ng <= 4096
+ * workspace: >= the bytes cft_eval_curves_workspace_bytes(n, nc, &bytes) gives, 256-byte aligned; the layout is cft_eval_ap's, so
+ * a buffer sized for one call serves the other.  Its contents after the call are unspecified.  Every argument is checked before the
+ * first launch (CFT_EINVAL, nothing launched).  No allocation, no synchronisation, no atomics: two calls give the same bits.
+ */
+int cft_eval_curves_workspace_bytes(long n, int nc, long* bytes);
+int cft_eval_curves(const unsigned short* tp_bits, const float* conf, const int* pcls, long n, const int* label_hist, int nc, int n_images,
+                    const double* px, const double* fppi_grid, const double* fppi_grid_host, int ng, void* workspace, long workspace_bytes,
+                    double* pcurve, double* rcurve, double* f1curve, double* pycurve, double* mr, int* best, void* stream);
+
+/*
  * cft_eval_confusion replaces ConfusionMatrix.process_batch (utils/metrics.py:119-157) as test.py:193-194 feeds it, for a whole
  * batch: the grouping launch of cft_eval_match, then one workgroup per image.  An image counts only if it has a label and an
  * NMS detection (test.py:140-143, :186).  Detections are kept if conf > conf_thres, classes are truncated toward zero (.int()),

@@ -179,43 +179,8 @@ extern "C" int cft_eval_match(const float* dets, const int* counts, int B, int m
 // ---------------------------------------------------------------------------------------------------------------------
 // (b) ap_per_class
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int SORT_THREADS = 256;
-constexpr int SORT_ITEMS = 16;
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;      // elements per workgroup of one radix pass
 constexpr int SCAN_THREADS = 1024;
-constexpr int CURVE_THREADS = 256;
-static_assert(CURVE_THREADS == MATCH_THREADS, "ap_curve_kernel uses block_excl_scan");
-constexpr int NPX = 1000;                                 // np.linspace(0, 1, 1000) (utils/metrics.py:40)
 constexpr int NX = 101;                                   // np.linspace(0, 1, 101) (utils/metrics.py:97)
-
-struct ApWs {
-  unsigned* key[2];
-  int* idx[2];
-  unsigned* hist;     // [256 * nblk] per-pass digit counts, digit-major, scanned in place
-  int* seg;           // [2 * (nc + 1)] start / end of each class in the sorted order
-  double* pcurve;     // [nc, NPX]
-  double* rcurve;     // [nc, NPX]
-};
-static inline int sort_blocks(long n) { return (int)((n + SORT_TILE - 1) / SORT_TILE); }
-static inline size_t ap_ws_layout(long n, int nc, char* base, ApWs* w) {
-  size_t o = 0;
-  const size_t nn = n > 0 ? (size_t)n : 1;
-  for (int i = 0; i < 2; ++i) {
-    if (w) w->key[i] = (unsigned*)(base + o);
-    o = align256(o + nn * 4);
-    if (w) w->idx[i] = (int*)(base + o);
-    o = align256(o + nn * 4);
-  }
-  if (w) w->hist = (unsigned*)(base + o);
-  o = align256(o + (size_t)256 * (sort_blocks(n) > 0 ? sort_blocks(n) : 1) * 4);
-  if (w) w->seg = (int*)(base + o);
-  o = align256(o + (size_t)2 * (nc + 1) * 4);
-  if (w) w->pcurve = (double*)(base + o);
-  o = align256(o + (size_t)nc * NPX * 8);
-  if (w) w->rcurve = (double*)(base + o);
-  o = align256(o + (size_t)nc * NPX * 8);
-  return o;
-}
 
 // conf -> key whose ascending order is descending conf (-0.0 folded onto +0.0, as np.argsort(-conf) sees them equal)
 __device__ __forceinline__ unsigned conf_key_desc(float c) {
@@ -346,29 +311,6 @@ __device__ double np_sum_small(const double* a, int len) {
   return a[0] + res;
 }
 
-// np.interp between two nodes (numpy's rule: j = last node with xp[j] <= x; an exact hit gives fp[j], else slope*(x - xp[j]) + fp[j],
-// retried from the right node if that is NaN)
-__device__ __forceinline__ double np_interp_seg(double x, double xa, double ya, double xb, double yb) {
-  if (x == xa) return ya;
-  const double slope = (yb - ya) / (xb - xa);
-  double v = slope * (x - xa) + ya;
-  if (v != v) {
-    v = slope * (x - xb) + yb;
-    if (v != v && ya == yb) v = ya;
-  }
-  return v;
-}
-
-// first index q of the ascending grid g[0..len) with g[q] >= v (upper = false) or g[q] > v (upper = true)
-__device__ __forceinline__ int grid_bound(const double* g, int len, double v, bool upper) {
-  int lo = 0, hi = len;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (upper ? (g[mid] <= v) : (g[mid] < v)) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // One workgroup per (class c, IoU column j) of a class with labels (utils/metrics.py:42-66, compute_ap :74-101).  The class's
 // predictions are walked from the last (lowest conf) to the first, 256 at a time: exact integer TP counts from the end, the
 // precision envelope of compute_ap (a reverse running max) as a running max, and every node of mrec writes the values of the
@@ -495,49 +437,8 @@ __global__ void __launch_bounds__(1024) ap_f1_kernel(const int* __restrict__ lab
   __shared__ double s_v[16];
   __shared__ int s_i[16];
   __shared__ int s_best;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double m = 0.0;
-  int mi = -1;
-  if (tid < NPX) {
-    double sum = 0.0;
-    int u = 0;
-    bool first = true;
-    for (int c = 0; c < nc; ++c) {
-      if (label_hist[c] <= 0) continue;
-      const double p = pcurve[(long)c * NPX + tid], r = rcurve[(long)c * NPX + tid];
-      const double f = 2.0 * p * r / (p + r + 1e-16);
-      sum = first ? f : sum + f;
-      first = false;
-      ++u;
-    }
-    m = sum / (double)u;
-    mi = tid;
-  }
-  // argmax, first index on ties (a NaN wins, as np.argmax)
-  auto better = [](double a, int ai, double b, int bi) {
-    if (ai < 0) return false;
-    if (bi < 0) return true;
-    if (b != b) return a != a && ai < bi;
-    if (a != a) return true;
-    return a > b || (a == b && ai < bi);
-  };
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double v2 = __shfl_xor(m, o);
-    const int i2 = __shfl_xor(mi, o);
-    if (better(v2, i2, m, mi)) { m = v2; mi = i2; }
-  }
-  if (lane == 0) { s_v[wave] = m; s_i[wave] = mi; }
-  __syncthreads();
-  if (tid == 0) {
-    double bv = s_v[0];
-    int bi = s_i[0];
-    for (int w = 1; w < 16; ++w)
-      if (better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
-    s_best = bi < 0 ? 0 : bi;
-  }
-  __syncthreads();
-  const int i = s_best;
+  const int tid = threadIdx.x;
+  const int i = f1_best_index(label_hist, nc, pcurve, rcurve, s_v, s_i, &s_best);
   for (int c = tid; c < nc; c += 1024) {
     if (label_hist[c] <= 0) { p_out[c] = 0.0; r_out[c] = 0.0; f1_out[c] = 0.0; continue; }
     const double p = pcurve[(long)c * NPX + i], r = rcurve[(long)c * NPX + i];
@@ -550,17 +451,8 @@ extern "C" long cft_eval_ap_workspace_bytes(long n, int nc) {
   return (long)ap_ws_layout(n, nc, nullptr, nullptr);
 }
 
-extern "C" int cft_eval_ap(const unsigned short* tp_bits, const float* conf, const int* pcls, long n, int niou, const int* label_hist, int nc,
-                           const double* px, const double* x, void* workspace, long workspace_bytes, double* out, void* stream) {
-  CFT_REQUIRE(label_hist && px && x && workspace && out, "cft_eval_ap: null pointer");
-  CFT_REQUIRE(n >= 0 && n < (1L << 30) && (n == 0 || (tp_bits && conf && pcls)), "cft_eval_ap: bad n (0 <= n < 2^30)");
-  CFT_REQUIRE(niou >= 1 && niou <= EVAL_MAX_IOU, "cft_eval_ap: niou must be in [1, 16]");
-  CFT_REQUIRE(nc >= 1 && nc <= 65535, "cft_eval_ap: nc must be in [1, 65535]");
-  CFT_REQUIRE(workspace_bytes >= (long)ap_ws_layout(n, nc, nullptr, nullptr), "cft_eval_ap: workspace too small (see cft_eval_ap_workspace_bytes)");
-  CFT_REQUIRE(((size_t)workspace & 255) == 0, "cft_eval_ap: workspace must be 256-byte aligned");
-  hipStream_t st = as_stream(stream);
-  ApWs w;
-  ap_ws_layout(n, nc, (char*)workspace, &w);
+// The sort of cft_eval_ap, also run by cft_eval_curves (curves.hip); the contract is at its declaration in metrics_common.h.
+int eval_sort_launch(const float* conf, const int* pcls, long n, const int* label_hist, int nc, const ApWs& w, int* cur_out, hipStream_t st) {
   const int nn = (int)n, nblk = sort_blocks(n), nseg = 2 * (nc + 1);
   const int gi = (int)((std::max<long>(n, nseg) + SORT_THREADS - 1) / SORT_THREADS);
   int cur = 0;
@@ -591,6 +483,24 @@ extern "C" int cft_eval_ap(const unsigned short* tp_bits, const float* conf, con
     hipLaunchKernelGGL(ap_segments_kernel, dim3(nblk * SORT_ITEMS), dim3(SORT_THREADS), 0, st, w.key[cur], nn, nc, w.seg);
     if ((rc = cft_check_launch("ap_segments_kernel")) != CFT_OK) return rc;
   }
+  *cur_out = cur;
+  return CFT_OK;
+}
+
+extern "C" int cft_eval_ap(const unsigned short* tp_bits, const float* conf, const int* pcls, long n, int niou, const int* label_hist, int nc,
+                           const double* px, const double* x, void* workspace, long workspace_bytes, double* out, void* stream) {
+  CFT_REQUIRE(label_hist && px && x && workspace && out, "cft_eval_ap: null pointer");
+  CFT_REQUIRE(n >= 0 && n < (1L << 30) && (n == 0 || (tp_bits && conf && pcls)), "cft_eval_ap: bad n (0 <= n < 2^30)");
+  CFT_REQUIRE(niou >= 1 && niou <= EVAL_MAX_IOU, "cft_eval_ap: niou must be in [1, 16]");
+  CFT_REQUIRE(nc >= 1 && nc <= 65535, "cft_eval_ap: nc must be in [1, 65535]");
+  CFT_REQUIRE(workspace_bytes >= (long)ap_ws_layout(n, nc, nullptr, nullptr), "cft_eval_ap: workspace too small (see cft_eval_ap_workspace_bytes)");
+  CFT_REQUIRE(((size_t)workspace & 255) == 0, "cft_eval_ap: workspace must be 256-byte aligned");
+  hipStream_t st = as_stream(stream);
+  ApWs w;
+  ap_ws_layout(n, nc, (char*)workspace, &w);
+  int cur = 0;
+  int rc = eval_sort_launch(conf, pcls, n, label_hist, nc, w, &cur, st);
+  if (rc != CFT_OK) return rc;
   // out = [p nc | r nc | f1 nc | ntp nc | ap nc * niou]
   double* p_out = out;
   double* r_out = out + nc;

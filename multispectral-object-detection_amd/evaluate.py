@@ -23,8 +23,12 @@ The rest of what ``python test.py`` gives is behind keywords that are off by def
 
 * ``plots``        the batch mosaics of test.py's ``plots=True`` (:220-225): for the first three batches
                    ``save_dir/test_batch{i}_labels.jpg`` and ``test_batch{i}_pred.jpg`` (``utils.plots.plot_images``, built on the
-                   device) with their ``_ir`` twins for the second stream, twelve files.  The PR / F1 curve images and the
-                   confusion-matrix image of ``plots=True`` are not drawn.
+                   device) with their ``_ir`` twins for the second stream, twelve files, and nothing else;
+* ``curves``       the curve images of test.py's ``plots=True`` (utils/metrics.py:71-75): ``save_dir/PR_curve.png``, ``F1_curve.png``,
+                   ``P_curve.png`` and ``R_curve.png``, and ``MR_curve.png``, the miss rate over false positives per image with the
+                   log-average miss rate (``utils.metrics.curves_per_class`` defines it); with ``confusion`` also
+                   ``confusion_matrix.png`` (test.py:239).  The numbers come from one more device stage after the statistics
+                   (``DetectionEvaluator.curves``, one more synchronisation); matplotlib draws them on the host.
 
 The values written come from one kernel (``cft_eval_export``) and one device-to-host copy per batch: the only added
 synchronisation, and only when a save option is on.  wandb logging and pycocotools scoring are not done.
@@ -102,9 +106,22 @@ def _plot_batch(pool, img, targets, paths, fname, names, device_jpeg=False):
     return pool.submit(_save_mosaics, host, event, flag, mosaic_file_names(fname, len(host)))
 
 
+def _save_curves(cv, res, ev, save_dir, names):
+    """``curves``: the images of utils/metrics.py:71-75 and test.py:239 from the host copies, plus the MR curve."""
+    from .utils import metrics
+    names = names if names is not None else ()
+    ap = res.ap if len(cv.ap_class) == len(res.ap_class) else [[0.0]] * len(cv.ap_class)      # no TP at all: test.py reports zeros
+    metrics.plot_pr_curve(cv, ap, save_dir, names)
+    for which in ("f1", "p", "r"):
+        metrics.plot_mc_curve(cv, which, save_dir, names)
+    metrics.plot_mr_curve(cv, save_dir, names)
+    if ev.confusion_matrix is not None:
+        ev.confusion_matrix.plot(save_dir=save_dir, names=list(names.values()) if isinstance(names, dict) else list(names))
+
+
 def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None, confusion=False,
              save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None, plots=False, names=None,
-             device_jpeg=False):
+             device_jpeg=False, curves=False):
     """batches: an iterable of ``(img6_uint8 [B, 6, H, W], targets [nt, 6], paths, shapes)`` as test.py's dataloader yields.
     Returns test.py's ``((mp, mr, map50, map75, map), maps)``; with ``compute_loss``, test.py's
     ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches.
@@ -117,10 +134,15 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
     ``device_jpeg``: the mosaics are encoded by ``utils.jpeg.encode_jpeg_start`` (device DCT, Huffman coding on the same pool) instead
     of by PIL; the files hold the same bytes.
 
+    ``curves`` (needs a ``save_dir``): the five curve images (module docstring), with ``confusion`` the confusion-matrix image too, named
+    with ``names``.  It adds no element to the return value either.
+
     ``details``: a dict that receives ``"result"``, the ``EvalResult`` behind the returned tuple (per-class p / r / ap, nt, seen - what
-    test.py's table prints, tools/val.py); the return value does not change."""
+    test.py's table prints, tools/val.py) and, with ``curves``, ``"curves"``, the ``EvalCurves``; the return value does not change."""
     if plots and save_dir is None:
         raise ValueError("evaluate: plots needs a save_dir")
+    if curves and save_dir is None:
+        raise ValueError("evaluate: curves needs a save_dir")
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model must be on the GPU (this package has no CPU path)")
@@ -130,7 +152,7 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
         if save_dir is None:
             raise ValueError("evaluate: save_txt / save_hybrid need a save_dir")
         (Path(save_dir) / 'labels').mkdir(parents=True, exist_ok=True)    # test.py:54
-    if plots:
+    if plots or curves:
         Path(save_dir).mkdir(parents=True, exist_ok=True)
     pool, jobs = (ThreadPoolExecutor(max_workers=4), []) if plots else (None, [])
     jdict = [] if save_json else None
@@ -176,6 +198,11 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
     res = ev.compute()
     if details is not None:
         details["result"] = res
+    if curves:
+        cv = ev.curves()
+        if details is not None:
+            details["curves"] = cv
+        _save_curves(cv, res, ev, save_dir, names)
     results, maps = res.as_test_tuple()
     if compute_loss is not None:
         losses = (loss.cpu() / nb).tolist() if nb else [0.0, 0.0, 0.0]          # test.py:295

@@ -10,6 +10,10 @@ matched detection) and then runs ``ap_per_class`` (``utils/metrics.py:18-108``) 
                            ``test.py``'s metrics with one synchronisation;
 * ``ConfusionMatrix``      the reference's class (``utils/metrics.py:111-183``): ``process_batch`` per image as there, and a
                            batched ``update`` on the ``batched_nms`` output (``cft_eval_confusion``), accumulated on the device;
+* ``curves_per_class``     the curves behind it (``cft_eval_curves``, ``csrc/curves.hip``): what ``ap_per_class(plot=True)`` hands to the
+                           reference's plot functions, plus the miss rate over false positives per image and the log-average
+                           miss rate; ``DetectionEvaluator.curves()`` gives the same from the accumulated batches, and
+                           ``plot_pr_curve`` / ``plot_mc_curve`` / ``plot_mr_curve`` draw them with matplotlib on the host;
 * ``export_batch``         the box values of ``save_txt`` / ``save_json`` for every detection slot (``cft_eval_export``);
                            ``txt_line`` and ``json_entry`` format them as ``test.py:156-158`` and ``:179-182`` do.
 
@@ -228,6 +232,220 @@ def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, save_dir='.', names
     p, r, f1, _, ap = _split(out, nc, niou)
     ap_class = np.flatnonzero(hist > 0)
     return p[ap_class], r[ap_class], ap[ap_class], f1[ap_class], ap_class.astype(np.int32)
+
+
+FPPI_REF = np.logspace(-2.0, 0.0, 9)         # the nine reference points of the log-average miss rate (Dollar et al.)
+FPPI_PLOT = np.logspace(-3, 1, 1000)         # default grid of the MR-FPPI plot
+MAX_FPPI_GRID = 4096                         # cft_eval_curves: values of the one grid handed to the device
+
+
+@dataclass
+class EvalCurves:
+    """The curves of a validation run, one row per class of ``ap_class`` (float64 numpy arrays).  ``py`` rows of a class with labels
+    and no predictions are zero (the reference's ``ap_per_class`` appends no row for such a class)."""
+    px: np.ndarray             # [1000] np.linspace(0, 1, 1000): confidence for p / r / f1, recall for py
+    py: np.ndarray             # [k, 1000] precision over recall at IoU 0.5 (PR_curve)
+    p: np.ndarray              # [k, 1000] precision over confidence (P_curve)
+    r: np.ndarray              # [k, 1000] recall over confidence (R_curve)
+    f1: np.ndarray             # [k, 1000] F1 over confidence (F1_curve)
+    best: int                  # f1.mean(0).argmax(): the px index at which ap_per_class reads p, r and f1
+    ap_class: np.ndarray       # [k] int32 classes with labels
+    fppi: np.ndarray           # [m] the plotting grid of false positives per image
+    mr_curve: np.ndarray       # [k, m] miss rate at fppi
+    mr_ref: np.ndarray         # [k, 9] miss rate at np.logspace(-2, 0, 9)
+    lamr: np.ndarray           # [k] log-average miss rate of each class
+    mlamr: float               # its mean over ap_class (0.0 without classes)
+
+
+def log_average_miss_rate(mr_ref):
+    """exp(mean(log(max(1e-10, mr)))) over the last axis: the geometric mean of the miss rate at the nine reference FPPI values."""
+    mr_ref = np.ascontiguousarray(mr_ref, dtype=np.float64)      # one summation order whatever layout the caller's array has
+    return np.exp(np.mean(np.log(np.maximum(1e-10, mr_ref)), axis=-1))
+
+
+def _fppi_grids(fppi_grid):
+    """(plotting grid, merged grid for the device, positions of the nine reference points, positions of the plotting grid)."""
+    plot = FPPI_PLOT if fppi_grid is None else np.asarray(fppi_grid, np.float64)
+    if plot.ndim != 1 or not 1 <= plot.size <= MAX_FPPI_GRID - FPPI_REF.size:
+        raise ValueError(f"curves: fppi_grid must be one-dimensional with 1 to {MAX_FPPI_GRID - FPPI_REF.size} values")
+    if not np.all(np.isfinite(plot)) or np.any(np.diff(plot) < 0):
+        raise ValueError("curves: fppi_grid must be finite and non-decreasing")
+    merged = np.sort(np.concatenate((FPPI_REF, plot)), kind="stable")
+    return plot, merged, np.searchsorted(merged, FPPI_REF), np.searchsorted(merged, plot)
+
+
+def _curves_device(tp_bits, conf, pcls, n, hist, nc, n_images, grid, device):
+    """cft_eval_curves on device buffers with the FPPI grid ``grid`` (host float64) -> one device float64 buffer
+    p | r | f1 | py (each nc * 1000) | mr (nc * len(grid)) | best (an int32 in the last slot).  No synchronisation."""
+    lib = _lib.load()
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    ng = int(grid.size)
+    px, _ = _grids(device)
+    nbytes = ctypes.c_long(0)
+    _lib.check(lib.cft_eval_curves_workspace_bytes(n, nc, ctypes.byref(nbytes)), "cft_eval_curves_workspace_bytes")
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=device)
+    k = nc * len(PX)
+    out = torch.empty((4 * k + nc * ng + 1,), dtype=torch.float64, device=device)
+    grid_dev = _to_device(torch.from_numpy(grid), device)
+    ptr = lambda t: t.data_ptr() if n else None  # noqa: E731
+    o = lambda i: out.data_ptr() + 8 * i  # noqa: E731
+    st = lib.cft_eval_curves(ptr(tp_bits), ptr(conf), ptr(pcls), n, hist.data_ptr(), nc, int(n_images), px.data_ptr(), grid_dev.data_ptr(),
+                             grid.ctypes.data, ng, ws.data_ptr(), ws.numel(), o(0), o(k), o(2 * k), o(3 * k), o(4 * k), o(4 * k + nc * ng),
+                             _stream())
+    _lib.check(st, "cft_eval_curves")
+    return out
+
+
+def _empty_curves(plot):
+    z = np.zeros((0, len(PX)))
+    return EvalCurves(PX.copy(), z, z.copy(), z.copy(), z.copy(), 0, np.zeros(0, np.int32), plot, np.zeros((0, plot.size)),
+                      np.zeros((0, FPPI_REF.size)), np.zeros(0), 0.0)
+
+
+def _curves_result(out, hist, nc, plot, merged, ref_at, plot_at):
+    """The host buffer of _curves_device -> EvalCurves over the classes with labels."""
+    k, ng = nc * len(PX), merged.size
+    ap_class = np.flatnonzero(hist[:nc] > 0)
+    if ap_class.size == 0:
+        return _empty_curves(plot)
+    p, r, f1, py = (out[i * k:(i + 1) * k].reshape(nc, len(PX))[ap_class] for i in range(4))
+    mr = out[4 * k:4 * k + nc * ng].reshape(nc, ng)[ap_class]
+    best = int(out[4 * k + nc * ng:].view(np.int32)[0])
+    # (C order: numpy sums a row of a column-gathered array in another order than a row of a contiguous one, a last-bit difference)
+    mr_ref, mr_curve = np.ascontiguousarray(mr[:, ref_at]), np.ascontiguousarray(mr[:, plot_at])
+    lamr = log_average_miss_rate(mr_ref)
+    return EvalCurves(PX.copy(), py, p, r, f1, best, ap_class.astype(np.int32), plot, mr_curve, mr_ref, lamr, float(lamr.mean()))
+
+
+def curves_per_class(tp, conf, pred_cls, target_cls, n_images, fppi_grid=None):
+    """The curves behind ``ap_per_class`` on the GPU (``cft_eval_curves``), from the same arrays: what the reference's
+    ``ap_per_class(plot=True)`` hands to its plot functions (py, p, r, f1 at the 1000 px points, utils/metrics.py:57-75), the px index it
+    reads its results at, and the miss rate over false positives per image with the log-average miss rate (``EvalCurves``).
+
+    ``n_images``: the images the statistics come from (``seen`` of test.py).  ``fppi_grid``: the plotting grid of the MR curve
+    (default ``np.logspace(-3, 1, 1000)``), non-decreasing.  The device walks ONE grid, the sorted merge of it and the nine reference
+    points ``np.logspace(-2, 0, 9)``; ``lamr`` is taken on the host.  The miss-rate definition is this package's (include/cft_hip.h):
+    the reference publishes LLVIP miss rates but ships no code for them."""
+    as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+    tp, conf, pred_cls, target_cls = as_np(tp), as_np(conf), as_np(pred_cls), as_np(target_cls)
+    if tp.ndim != 2 or not 1 <= tp.shape[1] <= 16:
+        raise ValueError(f"curves_per_class: tp must be [n, niou] with 1 <= niou <= 16, got {tp.shape}")
+    n = tp.shape[0]
+    if conf.shape != (n,) or pred_cls.shape != (n,):
+        raise ValueError(f"curves_per_class: conf and pred_cls must be [{n}], got {conf.shape} and {pred_cls.shape}")
+    tc = target_cls.astype(np.float64).reshape(-1)
+    if tc.size and (not np.all(tc >= 0) or not np.all(tc == np.floor(tc)) or tc.max() > 65534):
+        raise ValueError("curves_per_class: target classes must be integers in [0, 65534]")
+    if isinstance(n_images, bool) or int(n_images) != n_images or int(n_images) < 1:
+        raise ValueError(f"curves_per_class: n_images must be a positive integer, got {n_images}")
+    plot, merged, ref_at, plot_at = _fppi_grids(fppi_grid)
+    if not torch.cuda.is_available():
+        raise RuntimeError("curves_per_class: needs a GPU (this package has no CPU path; oracle/ and the tests hold CPU restatements)")
+    if tc.size == 0:
+        return _empty_curves(plot)
+    nc = int(tc.max()) + 1
+    hist = np.bincount(tc.astype(np.int64), minlength=nc).astype(np.int32)
+    pc = pred_cls.astype(np.float64)
+    ok = (pc >= 0) & (pc < nc) & (pc == np.floor(pc))
+    pci = np.where(ok, pc, -1).astype(np.int32)
+    bits = tp[:, 0].astype(bool).astype(np.uint16).view(np.int16) if n else np.zeros(0, np.int16)
+    device = torch.device("cuda", torch.cuda.current_device())
+    d = lambda a: _to_device(torch.from_numpy(np.ascontiguousarray(a)), device)  # noqa: E731
+    out = _curves_device(d(bits), d(conf.astype(np.float32)), d(pci), n, d(hist), nc, int(n_images), merged, device).cpu().numpy()
+    return _curves_result(out, hist, nc, plot, merged, ref_at, plot_at)
+
+
+def _class_name(names, c):
+    """The display name of class c: names may be a list or a dict, as in the reference; without one, the class number."""
+    try:
+        return str(names[int(c)])
+    except (KeyError, IndexError, TypeError):
+        return str(int(c))
+
+
+def _curve_figure(x, rows, classes, labels, mean, mean_label, xlabel, ylabel, logx=False):
+    """One line per class (named in the legend when there are fewer than 21, else thin grey) and a bold blue line for ``mean``."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    fig, ax = plt.subplots(1, 1, figsize=(9, 6), tight_layout=True)
+    few = 0 < len(classes) < 21
+    for i in range(len(classes)):
+        if few:
+            ax.plot(x, rows[i], linewidth=1, label=labels[i])
+        else:
+            ax.plot(x, rows[i], linewidth=1, color='grey')
+    if mean is not None:
+        ax.plot(x, mean, linewidth=3, color='blue', label=mean_label)
+    ax.set_xlabel(xlabel)
+    ax.set_ylabel(ylabel)
+    if logx:
+        ax.set_xscale('log')
+        ax.set_yscale('log')
+        ax.set_xlim(float(x[0]) if x[0] > 0 else 1e-3, float(x[-1]))
+        ax.set_ylim(1e-2, 1.0)
+        ax.grid(True, which='both', linewidth=0.3)
+    else:
+        ax.set_xlim(0, 1)
+        ax.set_ylim(0, 1)
+    return fig, ax, plt
+
+
+def plot_pr_curve(curves, ap, save_dir='.', names=()):
+    """``save_dir/PR_curve.png``: precision over recall at IoU 0.5 for every class of ``curves`` (an ``EvalCurves``), each named with
+    its AP@0.5, and their mean named with mAP@0.5.  ``ap``: ap_per_class's [k, niou] array (or its column 0).  Silent on failure."""
+    try:
+        ap = np.asarray(ap, np.float64)
+        ap50 = ap[:, 0] if ap.ndim == 2 else ap
+        labels = [f"{_class_name(names, c)} {a:.3f}" for c, a in zip(curves.ap_class, ap50)]
+        mean = curves.py.mean(0) if len(curves.ap_class) else None
+        fig, ax, plt = _curve_figure(curves.px, curves.py, curves.ap_class, labels, mean,
+                                     f"all classes {ap50.mean():.3f} mAP@0.5" if len(ap50) else None, 'Recall', 'Precision')
+        ax.legend(bbox_to_anchor=(1.04, 1), loc="upper left")
+        fig.savefig(Path(save_dir) / 'PR_curve.png', dpi=250)
+        plt.close(fig)
+    except Exception:
+        pass
+
+
+_MC_CURVES = {"f1": ("F1_curve.png", "F1"), "p": ("P_curve.png", "Precision"), "r": ("R_curve.png", "Recall")}
+
+
+def plot_mc_curve(curves, which, save_dir='.', names=()):
+    """``save_dir/F1_curve.png``, ``P_curve.png`` or ``R_curve.png`` (``which`` = 'f1', 'p' or 'r'): the metric over confidence for
+    every class and their mean, whose legend entry names its maximum and the confidence there.  Silent on failure (an unknown
+    ``which`` is an error)."""
+    if which not in _MC_CURVES:
+        raise ValueError(f"plot_mc_curve: which must be one of {sorted(_MC_CURVES)}, got {which!r}")
+    fname, ylabel = _MC_CURVES[which]
+    try:
+        rows = getattr(curves, which)
+        labels = [_class_name(names, c) for c in curves.ap_class]
+        mean = rows.mean(0) if len(curves.ap_class) else None
+        label = f"all classes {mean.max():.2f} at {curves.px[mean.argmax()]:.3f}" if mean is not None else None
+        fig, ax, plt = _curve_figure(curves.px, rows, curves.ap_class, labels, mean, label, 'Confidence', ylabel)
+        ax.legend(bbox_to_anchor=(1.04, 1), loc="upper left")
+        fig.savefig(Path(save_dir) / fname, dpi=250)
+        plt.close(fig)
+    except Exception:
+        pass
+
+
+def plot_mr_curve(curves, save_dir='.', names=()):
+    """``save_dir/MR_curve.png``: miss rate over false positives per image on log-log axes for every class, the nine reference
+    points marked, the log-average miss rate of each class (and the mean) in the legend.  Silent on failure."""
+    try:
+        labels = [f"{_class_name(names, c)} {100 * v:.2f}%" for c, v in zip(curves.ap_class, curves.lamr)]
+        fig, ax, plt = _curve_figure(curves.fppi, curves.mr_curve, curves.ap_class, labels, None, None, 'False positives per image',
+                                     'Miss rate', logx=True)
+        for i in range(len(curves.ap_class)):
+            ax.plot(FPPI_REF, curves.mr_ref[i], linestyle='none', marker='o', markersize=4, color='black')
+        ax.plot([], [], linestyle='none', marker='o', markersize=4, color='black', label=f"mean MR^-2 {100 * curves.mlamr:.2f}%")
+        ax.legend(bbox_to_anchor=(1.04, 1), loc="upper left")
+        fig.savefig(Path(save_dir) / 'MR_curve.png', dpi=250)
+        plt.close(fig)
+    except Exception:
+        pass
 
 
 def _geom_device(shapes, img_hw, B, device, what):
@@ -516,3 +734,18 @@ class DetectionEvaluator:
             maps[c] = apm[i]
         return EvalResult(float(mp), float(mr), float(map50), float(map75), float(map_), maps, p, r, ap, f1, ap_class.astype(np.int32),
                           nt, self.seen, cm)
+
+    def curves(self, fppi_grid=None):
+        """The curves of the accumulated statistics (``EvalCurves``, see ``curves_per_class``) with ``seen`` as the image count: two
+        launches after the sort of ``compute()``, which it repeats on a workspace of its own, and one synchronisation.  ``compute()`` is
+        not needed before it and is not changed by it.  Before any ``update()`` it returns empty arrays."""
+        plot, merged, ref_at, plot_at = _fppi_grids(fppi_grid)
+        if self._hist is None:
+            return _empty_curves(plot)
+        nc = self.nc
+        out = _curves_device(self._tp, self._conf, self._pcls, self.n, self._hist, nc, max(self.seen, 1), merged, self.device)
+        both = torch.cat((out.view(torch.int32), self._hist)).cpu().numpy()       # the one synchronisation
+        hist = both[-(nc + 1):]
+        if hist[nc]:
+            raise ValueError(f"DetectionEvaluator: {int(hist[nc])} labels have a class outside [0, {nc})")
+        return _curves_result(both[:-(nc + 1)].view(np.float64), hist, nc, plot, merged, ref_at, plot_at)

@@ -5,7 +5,8 @@
 Per 64-image batch (300 detections and 20 labels per image, 3 classes): match_batch + DetectionEvaluator.update
 versus a per-image / per-class Python loop in the style of test.py:132-218 (written here from the rules, on the
 same GPU tensors).  Then DetectionEvaluator.compute() (ap_per_class) for 1013 x 300 detections with 3 classes and
-5000 x 300 with 80 classes.  The confusion / export leg times, on the same 64-image batch and alternating the sides round by
+5000 x 300 with 80 classes, taking turns with DetectionEvaluator.curves() (cft_eval_curves: the same sort, one more walk and a
+larger device-to-host copy) on the same statistics.  The confusion / export leg times, on the same 64-image batch and alternating the sides round by
 round: update() without and with confusion=True, a per-image process_batch loop in the reference's style (written here from
 the algorithm, on GPU tensors), the two confusion launches alone, the two matching launches alone, and export_batch with its
 device-to-host copy.  Both update() legs include their evaluator's reset(): the plain one reserves its statistics buffers again,
@@ -201,7 +202,8 @@ def main():
             ev.update(b64[0][:k].contiguous(), b64[1][:k].contiguous(), b64[2][b64[2][:, 0] < k], (H, W), b64[3][:k])
             left -= k
         torch.cuda.synchronize()
-        res[f"compute_ms_{name}"] = timed(ev.compute, a.reps) * 1e3
+        med = alternated({f"compute_ms_{name}": ev.compute, f"curves_ms_{name}": ev.curves}, a.reps, warm=1)
+        res.update({k: v * 1e3 for k, v in med.items()})
         res[f"map_{name}"] = ev.compute().map
     print(json.dumps(res))
 

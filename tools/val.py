@@ -1,6 +1,6 @@
 """Validate a checkpoint on a paired RGB + IR dataset on disk: the command-line form of the reference's test.py.
 
-    python tools/val.py DATA.yaml WEIGHTS.pt [--img-size 640] [--batch-size 32] [--single-cls] [--save-txt] [--save-json] [--plots] [--verbose]
+    python tools/val.py DATA.yaml WEIGHTS.pt [--img-size 640] [--batch-size 32] [--single-cls] [--save-txt] [--save-json] [--plots] [--curves] [--verbose]
 
 DATA.yaml holds ``val_rgb`` and ``val_ir`` (directories or *.txt lists; relative paths are taken from the yaml's directory), ``nc``
 and ``names``.  The loader is built as test.py builds it (:86-94: ``rect=True, pad=0.5``, the model's largest stride), every batch is
@@ -35,6 +35,7 @@ def main(argv=None):
     ap.add_argument("--save-txt", action="store_true")
     ap.add_argument("--save-json", action="store_true")
     ap.add_argument("--plots", action="store_true", help="test_batch{0,1,2}_{labels,pred}[_ir].jpg of the first three batches in --save-dir")
+    ap.add_argument("--curves", action="store_true", help="PR / F1 / P / R / MR curve images in --save-dir and an MR^-2 column (log-average miss rate)")
     ap.add_argument("--device-jpeg", action="store_true", help="encode the --plots mosaics on the GPU instead of with PIL (the same bytes)")
     ap.add_argument("--save-dir", default="runs/val")
     ap.add_argument("--workers", type=int, default=8)
@@ -73,18 +74,22 @@ def main(argv=None):
                          f"fix the labels or nc, or pass --single-cls")
     details = {}
     evaluate(model, loader, nc, conf_thres=opt.conf_thres, iou_thres=opt.iou_thres, single_cls=opt.single_cls, save_txt=opt.save_txt,
-             save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json or opt.plots) else None, details=details,
-             plots=opt.plots, names=names if opt.plots else None, device_jpeg=opt.device_jpeg)
+             save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json or opt.plots or opt.curves) else None,
+             details=details, plots=opt.plots, names=names if (opt.plots or opt.curves) else None, device_jpeg=opt.device_jpeg, curves=opt.curves)
     res = details["result"]
+    cv = details.get("curves")
+    lamr = {int(c): v for c, v in zip(cv.ap_class, cv.lamr)} if cv is not None else {}
 
-    print(('%20s' + '%12s' * 7) % ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.75', 'mAP@.5:.95'))
-    pf = '%20s' + '%12i' * 2 + '%12.3g' * 5  # print format
-    print(pf % ('all', res.seen, int(res.nt.sum()), res.mp, res.mr, res.map50, res.map75, res.map))
+    cols = ('Class', 'Images', 'Labels', 'P', 'R', 'mAP@.5', 'mAP@.75', 'mAP@.5:.95') + (('MR^-2',) if cv is not None else ())
+    print(('%20s' + '%12s' * (len(cols) - 1)) % cols)
+    pf = '%20s' + '%12i' * 2 + '%12.3g' * (len(cols) - 3)  # print format
+    print(pf % (('all', res.seen, int(res.nt.sum()), res.mp, res.mr, res.map50, res.map75, res.map) + ((cv.mlamr,) if cv is not None else ())))
     if (opt.verbose or nc < 50) and nc > 1 and len(res.ap_class):
         ap = res.ap
         for i, c in enumerate(res.ap_class):
-            print(pf % (names[c] if c < len(names) else str(c), res.seen, res.nt[c], res.p[i], res.r[i], ap[i, 0], ap[i, 5], ap[i].mean()))
-    if opt.save_txt or opt.save_json or opt.plots:
+            print(pf % ((names[c] if c < len(names) else str(c), res.seen, res.nt[c], res.p[i], res.r[i], ap[i, 0], ap[i, 5], ap[i].mean())
+                        + ((lamr[int(c)],) if cv is not None else ())))
+    if opt.save_txt or opt.save_json or opt.plots or opt.curves:
         print(f"Results saved to {opt.save_dir}")
     return res
 
