@@ -941,6 +941,35 @@ int cft_ema_update(const void* table_dev, const void* table_host, int nseg, long
 int cft_adam_step(const void* table_dev, const void* table_host, int nseg, long nwork, int chunk, int max_blocks,
                   const double* hyper_host, int ngroups, float* coef, const float* grad_scale, const float* found_inf, void* stream);
 
+/*
+ * Test-time augmentation of the single-stream model (reference models/yolo.py:113-128: scales 1 / 0.83 / 0.67, the middle view
+ * mirrored left-right).  Two entry points, each one launch on the caller's stream; no allocation, no synchronisation, no atomics,
+ * every output element written once: two runs give the same bits.  Every argument is checked on the host before the launch and
+ * nothing is launched on CFT_EINVAL.
+ *
+ * cft_tta_view: scale_img (utils/torch_utils.py:247-257) of one view.  img is the [B, 3, H, W] batch, dtype CFT_TTA_U8 (each element
+ * read as (float)u8 / 255.0f, IEEE division), CFT_TTA_F16 or CFT_TTA_F32; sb, sc, sh, sw = element strides, so channels [3, 6) of a
+ * six-channel batch are a legal input.  ratio: host double in (0, 1]; gs >= 1 the grid size (the model's largest stride); flip 1 =
+ * the image is mirrored left-right first.  With hs = (int)(H * ratio), ws = (int)(W * ratio) in doubles (Python's int()):
+ *   resize  torch's bilinear with align_corners=False, every operation one float32 rounding, no fused multiply-add, per axis
+ *             scale = (float)in / (float)out;  src = max(scale * (dst + 0.5f) - 0.5f, 0);  i0 = min((int)floorf(src), in - 1);
+ *             i1 = min(i0 + 1, in - 1);  w1 = clamp(src - i0, 0, 1);  w0 = 1 - w1;
+ *           value = (p00 * wx0 + p01 * wx1) * wy0 + (p10 * wx0 + p11 * wx1) * wy1;  a mirrored image reads column W - 1 - i;
+ *   pad     rows >= hs and columns >= ws hold 0.447f, up to Ho = ceil(H * ratio / gs) * gs and Wo likewise (Python doubles);
+ *   out     float32 [B, 3, Ho, Wo], contiguous, 16-byte aligned; Ho and Wo are checked against the formula.
+ * The view of ratio 1 without a flip is the input itself (scale_img returns it); callers do not launch for it.
+ *
+ * cft_tta_merge: y0, y1, y2 = the views' float32 predictions [B, n_v, no] (contiguous) -> out [B, total, no], total = n0 + n1 + n2,
+ * view after view along the row axis.  Columns 0..3 are divided by s_v (IEEE float32 division, what torch's CPU `/=` computes for
+ * a Python scalar cast to float32); then column 0 of a view whose bit is set in flip_mask becomes img_w - x (one subtraction);
+ * every other column is copied.  s_v in (0, 1]; no >= 5; no input may overlap out.
+ */
+enum { CFT_TTA_U8 = 0, CFT_TTA_F16 = 1, CFT_TTA_F32 = 2 };
+int cft_tta_view(const void* img, int dtype, int B, int H, int W, long sb, long sc, long sh, long sw, const double* ratio, int gs,
+                 int flip, float* out, int Ho, int Wo, void* stream);
+int cft_tta_merge(const float* y0, const float* y1, const float* y2, int B, int n0, int n1, int n2, int no, float s0, float s1, float s2,
+                  int flip_mask, float img_w, float* out, int total, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: experiments with an alternative build, e.g. the probe library)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "curves.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip", "jpeg_encode.hip")
+SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "curves.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip", "jpeg_encode.hip", "tta.hip")
 
 HEADER = os.path.join(_HERE, "..", "include", "cft_hip.h")
 HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "resize_common.h", "jpeg_common.h", "conv_gemm_asm.inc")

@@ -3,11 +3,13 @@
 The reference's callers (`train.py:26-27`, `test.py`, `detect_twostream.py`) do
 ``from models.yolo_test import Model`` / ``from models.common import *`` and its checkpoints are
 pickled whole ``nn.Module`` objects (``train.py:850-860``) whose classes are recorded as
-``models.yolo_test.Model`` and ``models.common.<Class>``.  After
+``models.yolo_test.Model`` and ``models.common.<Class>``; the pretrained ``yolov5*.pt`` files its README
+starts from, and any single-modality baseline, are pickled ``models.yolo.Model`` objects (the single-stream file).  After
 ``install_reference_aliases()`` those names resolve to the MI355X-native classes, so
 
     import msod_amd.compat as c; c.install_reference_aliases()
     from models.yolo_test import Model            # -> msod_amd.models.yolo_test.Model
+    from models.yolo import Model as Single       # -> msod_amd.models.yolo.Model
     ckpt = torch.load("best.pt", weights_only=False)   # un-pickles into the HIP-backed modules
 
 works without touching the caller.  (Un-pickling restores parameters and buffers; the kernel-side
@@ -18,8 +20,8 @@ import types
 
 
 def install_reference_aliases(force=False):
-    from .models import common, yolo_test
-    for name, mod in (("models.common", common), ("models.yolo_test", yolo_test)):
+    from .models import common, yolo, yolo_test
+    for name, mod in (("models.common", common), ("models.yolo_test", yolo_test), ("models.yolo", yolo)):
         if name in sys.modules and sys.modules[name] is not mod and not force:
             raise RuntimeError(f"{name} is already imported from {getattr(sys.modules[name], '__file__', '?')}; "
                                "pass force=True to override it")
@@ -31,6 +33,7 @@ def install_reference_aliases(force=False):
         sys.modules["models"] = pkg
     pkg.common = common
     pkg.yolo_test = yolo_test
+    pkg.yolo = yolo
     return pkg
 
 
@@ -70,12 +73,29 @@ def _ensemble_class():
     return Ensemble
 
 
+def _single_ensemble_class():
+    import torch
+    import torch.nn as nn
+
+    class Ensemble(nn.ModuleList):
+        """Ensemble of single-stream models: the reference's own one-input form (models/experimental.py:98-110), the members'
+        prediction tensors concatenated along the box axis."""
+
+        def forward(self, x, augment=False):
+            y = [module(x, augment)[0] for module in self]
+            return torch.cat(y, 1), None
+
+    return Ensemble
+
+
 def attempt_load(weights, map_location=None):
     """The reference's ``attempt_load`` (models/experimental.py:113-134): ``weights`` is one checkpoint path or a
     list of them; each pickled checkpoint -> ``ema`` or ``model`` -> ``.float().fuse().eval()`` (an fp32 model,
     as in the reference: callers then opt into 16-bit with ``model.half()``, test.py:66-68, or with
     ``set_compute_dtype``).  One path returns the model, several return an ``Ensemble`` carrying the last
-    member's ``names`` / ``stride`` (:129-133)."""
+    member's ``names`` / ``stride`` (:129-133).  A checkpoint of the single-stream file (``models.yolo.Model``) loads into this
+    package's single-stream ``Model``; a list of them gives the one-input ``Ensemble.forward(x, augment=False)``; a list that
+    mixes the two kinds cannot be called with one signature and raises, naming a file of each kind."""
     import torch
     install_reference_aliases()
     members = []
@@ -86,7 +106,12 @@ def attempt_load(weights, map_location=None):
         members.append(model.float().fuse().eval())
     if len(members) == 1:
         return members[-1]
-    ens = _ensemble_class()()
+    files = list(weights)
+    kinds = [getattr(m, "inputs", 2) for m in members]
+    if len(set(kinds)) > 1:
+        raise ValueError(f"attempt_load: {files[kinds.index(1)]} is a single-stream checkpoint (models.yolo.Model) and "
+                         f"{files[kinds.index(2)]} a two-stream one (models.yolo_test.Model); an ensemble takes one kind")
+    ens = (_single_ensemble_class() if kinds[0] == 1 else _ensemble_class())()
     for m in members:
         ens.append(m)
     for k in ("names", "stride"):

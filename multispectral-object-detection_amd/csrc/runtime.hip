@@ -20,7 +20,7 @@ int cft_check_launch(const char* what) {
   return CFT_OK;
 }
 
-extern "C" int cft_abi_version(void) { return CFT_ABI_VERSION; }   // 2: CFT_F16, dtype arguments of cft_bottleneck / cft_focus_conv, cft_to_nhwc; 3: w2_stages; 4: round 3 (probe exports removed, w2_stages required, permuted-row weights); 5: cft_clock_probe; 6: cft_gpt_upsample_add2, per-thread conv variant; 7: cft_conv2d_chain; 8: cft_conv2d_chain_ok takes ldx / ldy (the launcher's own validation); 9: cft_conv2d_chain_res, cft_linear_splitk, cft_layernorm_reduce; 10: cft_stem; 11: cft_stem / cft_stem_ok removed (probe build only), cft_set_conv_variant 96 / 961-964 / 97; 12: cft_gpt_tokenize_grid, cft_attention_tokens, cft_gpt_upsample_add{,2}_grid (any anchor grid); 13: cft_eval_match, cft_eval_ap (+ workspace queries); 14: cft_loss_forward, cft_loss_backward (+ cft_loss_workspace_bytes, cft_loss_workspace_offsets); 15: cft_eval_confusion (+ cft_eval_confusion_workspace_bytes), cft_eval_export; 16: cft_anchor_metric, cft_anchor_kmeans, cft_anchor_evolve (+ their workspace queries); 17: cft_pair_batch_u8; 18: cft_detect_boxes, cft_detect_render; 19: cft_sgd_step, cft_ema_update (added since without a new number, nothing existing changed: cft_mosaic_compose / _slots / _finish / _area, the cft_detect_render flags CFT_RENDER_CONF1 and CFT_RENDER_SIGNED, cft_adam_step; a library without them fails to load, _lib.load binds every declared name)
+extern "C" int cft_abi_version(void) { return CFT_ABI_VERSION; }   // 2: CFT_F16, dtype arguments of cft_bottleneck / cft_focus_conv, cft_to_nhwc; 3: w2_stages; 4: round 3 (probe exports removed, w2_stages required, permuted-row weights); 5: cft_clock_probe; 6: cft_gpt_upsample_add2, per-thread conv variant; 7: cft_conv2d_chain; 8: cft_conv2d_chain_ok takes ldx / ldy (the launcher's own validation); 9: cft_conv2d_chain_res, cft_linear_splitk, cft_layernorm_reduce; 10: cft_stem; 11: cft_stem / cft_stem_ok removed (probe build only), cft_set_conv_variant 96 / 961-964 / 97; 12: cft_gpt_tokenize_grid, cft_attention_tokens, cft_gpt_upsample_add{,2}_grid (any anchor grid); 13: cft_eval_match, cft_eval_ap (+ workspace queries); 14: cft_loss_forward, cft_loss_backward (+ cft_loss_workspace_bytes, cft_loss_workspace_offsets); 15: cft_eval_confusion (+ cft_eval_confusion_workspace_bytes), cft_eval_export; 16: cft_anchor_metric, cft_anchor_kmeans, cft_anchor_evolve (+ their workspace queries); 17: cft_pair_batch_u8; 18: cft_detect_boxes, cft_detect_render; 19: cft_sgd_step, cft_ema_update (added since without a new number, nothing existing changed: cft_mosaic_compose / _slots / _finish / _area, the cft_detect_render flags CFT_RENDER_CONF1 and CFT_RENDER_SIGNED, cft_adam_step, cft_tta_view / _merge; a library without them fails to load, _lib.load binds every declared name)
 
 extern "C" const char* cft_last_error(void) { return g_err; }
 

@@ -30,6 +30,10 @@ The rest of what ``python test.py`` gives is behind keywords that are off by def
                    ``confusion_matrix.png`` (test.py:239).  The numbers come from one more device stage after the statistics
                    (``DetectionEvaluator.curves``, one more synchronisation); matplotlib draws them on the host.
 
+A single-stream model (``models.yolo.Model``, a single-modality baseline) is evaluated on the same paired loader: ``modality='rgb'`` or
+``'ir'`` picks channels [0:3] or [3:6] of each batch (a view, not a copy), and ``augment=True`` - test.py's ``--augment`` - runs its
+test-time augmentation.  Everything behind the forward is the same code.  With a two-stream model ``modality`` is refused and ``augment`` meets ``Model.forward``'s own refusal.
+
 The values written come from one kernel (``cft_eval_export``) and one device-to-host copy per batch: the only added
 synchronisation, and only when a save option is on.  wandb logging and pycocotools scoring are not done.
 """
@@ -121,7 +125,7 @@ def _save_curves(cv, res, ev, save_dir, names):
 
 def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=False, compute_loss=None, confusion=False,
              save_txt=False, save_conf=False, save_hybrid=False, save_json=False, save_dir=None, details=None, plots=False, names=None,
-             device_jpeg=False, curves=False):
+             device_jpeg=False, curves=False, modality=None, augment=False):
     """batches: an iterable of ``(img6_uint8 [B, 6, H, W], targets [nt, 6], paths, shapes)`` as test.py's dataloader yields.
     Returns test.py's ``((mp, mr, map50, map75, map), maps)``; with ``compute_loss``, test.py's
     ``((mp, mr, map50, map75, map, box, obj, cls), maps)``, the losses averaged over the batches.
@@ -137,12 +141,25 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
     ``curves`` (needs a ``save_dir``): the five curve images (module docstring), with ``confusion`` the confusion-matrix image too, named
     with ``names``.  It adds no element to the return value either.
 
+    ``modality`` ('rgb' | 'ir') and ``augment``: for a single-stream model only (module docstring); with ``augment`` the forward returns no
+    raw list, so it cannot be combined with ``compute_loss``.
+
     ``details``: a dict that receives ``"result"``, the ``EvalResult`` behind the returned tuple (per-class p / r / ap, nt, seen - what
     test.py's table prints, tools/val.py) and, with ``curves``, ``"curves"``, the ``EvalCurves``; the return value does not change."""
     if plots and save_dir is None:
         raise ValueError("evaluate: plots needs a save_dir")
     if curves and save_dir is None:
         raise ValueError("evaluate: curves needs a save_dir")
+    single = getattr(model, "inputs", 2) == 1
+    if single:
+        if modality not in ("rgb", "ir"):
+            raise ValueError(f"evaluate: a single-stream model needs modality='rgb' or 'ir', got {modality!r}")
+        if augment and compute_loss is not None:
+            raise ValueError("evaluate: augment=True returns no raw outputs (models/yolo.py:128); the loss cannot be computed with it")
+        c0 = 0 if modality == "rgb" else 3
+    else:
+        if modality is not None:
+            raise ValueError("evaluate: modality selects the input of a single-stream model; a two-stream model takes both streams")
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model must be on the GPU (this package has no CPU path)")
@@ -166,7 +183,10 @@ def evaluate(model, batches, nc, conf_thres=0.001, iou_thres=0.6, single_cls=Fal
             img = img.pin_memory().to(device, non_blocking=True) if img.device.type == "cpu" else img.to(device)
         H, W = img.shape[2], img.shape[3]
         with torch.no_grad():
-            res = model(img[:, :3], img[:, 3:])
+            if single:
+                res = model(img[:, c0:c0 + 3], augment=augment)
+            else:                                                          # (augment: Model.forward's own refusal answers)
+                res = model(img[:, :3], img[:, 3:], augment=True) if augment else model(img[:, :3], img[:, 3:])
             out = res[0]
             if compute_loss is not None:                                   # test.py:121-123, normalised targets
                 loss += compute_loss([x.float().contiguous() for x in res[1]], targets)[1][:3]

@@ -1,4 +1,4 @@
-"""HIP-graph capture of the whole two-stream forward.
+"""HIP-graph capture of the whole forward (two-stream, or single-stream: ``model.inputs`` image batches).
 
 yolov5l + CFTx3 is ~600 kernel launches per forward; launched one by one from Python the host
 becomes the bottleneck well before the GPU does.  ``CapturedForward`` records the launches
@@ -15,23 +15,25 @@ class CapturedForward:
         if dev.type != "cuda":
             raise RuntimeError("capture: model must be on the GPU")
         self.rgb = torch.zeros((batch, 3, height, width), dtype=input_dtype, device=dev)
-        self.ir = torch.zeros_like(self.rgb)
+        self.ir = torch.zeros_like(self.rgb) if getattr(model, "inputs", 2) == 2 else None       # a single-stream model has one input
+        ins = (self.rgb,) if self.ir is None else (self.rgb, self.ir)
         model.prepare()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(warmup):                  # first launches set kernel attributes, pack weights
-                model.forward_once(self.rgb, self.ir, until_detect=True)
+                model.forward_once(*ins, until_detect=True)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.pred, self.raw = model.forward_once(self.rgb, self.ir, until_detect=True)
+            self.pred, self.raw = model.forward_once(*ins, until_detect=True)
         self.weights_key = model.weights_key()     # Model.forward drops the graph when the weights change
 
-    def replay(self, rgb, ir):
+    def replay(self, rgb, ir=None):
         self.rgb.copy_(rgb, non_blocking=True)
-        self.ir.copy_(ir, non_blocking=True)
+        if self.ir is not None:
+            self.ir.copy_(ir, non_blocking=True)
         self.graph.replay()
         return self.pred, self.raw
 

@@ -163,6 +163,22 @@ REFERENCE_YAMLS = {
 }
 
 
+# the single-stream yamls of the reference's models/ directory: one layer list, four (depth, width) multiples, nc 80
+STOCK_YAMLS = {"yolov5s": "s", "yolov5m": "m", "yolov5l": "l", "yolov5x": "x"}
+
+
+def stock_config(name, nc=80, anchors=None):
+    """The dict ``yaml.safe_load`` gives for the reference's ``models/<name>.yaml`` (``name`` in ``STOCK_YAMLS``), with Upsample's size
+    as None (the yaml writes the string 'None'; ``parse_model`` reads both).  One CSPDarknet backbone and the PANet head of
+    ``_head``, whose lateral inputs here are backbone rows 4 (P3) and 6 (P4)."""
+    gd, gw = SIZES[STOCK_YAMLS[name]]
+    st = _stem()
+    st[0][0] = -1
+    backbone = st + _stage(-1, 256, 9) + _stage(-1, 512, 9) + _top(-1)
+    return {"nc": nc, "depth_multiple": gd, "width_multiple": gw, "anchors": deepcopy(anchors or ANCHORS), "backbone": backbone,
+            "head": _head(4, 6, True, len(backbone))}
+
+
 def named_config(name):
     """BASELINE.json configs by short name."""
     if name in REFERENCE_YAMLS:

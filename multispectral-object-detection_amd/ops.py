@@ -904,6 +904,60 @@ def mosaic_area(src, dh, dw):
     return dst
 
 
+# ------------------------------------------------------------------------------ test-time augmentation
+_TTA_DTYPES = {torch.uint8: "CFT_TTA_U8", torch.float16: "CFT_TTA_F16", torch.float32: "CFT_TTA_F32"}
+
+
+def tta_view_size(H, W, ratio, gs):
+    """``((hs, ws), (Ho, Wo))`` of one view: the scaled and the padded size of the reference's ``scale_img`` (utils/torch_utils.py:252-256)."""
+    import math
+    return (int(H * ratio), int(W * ratio)), tuple(math.ceil(x * ratio / gs) * gs for x in (H, W))
+
+
+def tta_view(img, ratio, gs, flip=False, out=None):
+    """cft_tta_view: the (possibly strided) ``[B, 3, H, W]`` uint8 / fp16 / fp32 batch -> one augmented view, fp32 ``[B, 3, Ho, Wo]``:
+    optional left-right flip, bilinear resize by ``ratio``, right / bottom padding with 0.447 to multiples of ``gs``."""
+    import ctypes
+    _require_cuda(img, "tta_view")
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype not in _TTA_DTYPES:
+        raise ValueError(f"tta_view: images must be a [B, 3, H, W] uint8, float16 or float32 tensor, got {img.dtype} {tuple(img.shape)}")
+    B, _, H, W = img.shape
+    if gs < 1:
+        raise ValueError(f"tta_view: gs must be >= 1, got {gs}")
+    _, (Ho, Wo) = tta_view_size(H, W, float(ratio), int(gs))
+    if out is None:
+        out = torch.empty((B, 3, Ho, Wo), dtype=torch.float32, device=img.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, Ho, Wo) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"tta_view: out must be a contiguous float32 CUDA tensor [{B}, 3, {Ho}, {Wo}]")
+    r = ctypes.c_double(float(ratio))
+    st = _lib.load().cft_tta_view(img.data_ptr(), _lib._consts[_TTA_DTYPES[img.dtype]], B, H, W, *img.stride(), ctypes.byref(r), int(gs),
+                                  int(bool(flip)), out.data_ptr(), Ho, Wo, _stream())
+    _lib.check(st, "cft_tta_view")
+    return out
+
+
+def tta_merge(preds, scales, flips, img_w, out=None):
+    """cft_tta_merge: the three views' fp32 predictions ``[B, n_v, no]`` -> ``[B, sum n_v, no]``; columns 0-3 divided by the view's scale,
+    column 0 of a flipped view replaced by ``img_w - x``."""
+    if len(preds) != 3 or len(scales) != 3 or len(flips) != 3:
+        raise ValueError("tta_merge: three views, three scales, three flips")
+    for p in preds:
+        _require_cuda(p, "tta_merge")
+        if p.dtype != torch.float32 or p.dim() != 3 or not p.is_contiguous() or p.shape[0] != preds[0].shape[0] or p.shape[2] != preds[0].shape[2]:
+            raise ValueError(f"tta_merge: predictions must be contiguous float32 [B, n, no] tensors of one B and no, got {p.dtype} {tuple(p.shape)}")
+    B, _, no = preds[0].shape
+    n = [p.shape[1] for p in preds]
+    if out is None:
+        out = torch.empty((B, sum(n), no), dtype=torch.float32, device=preds[0].device)
+    elif out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != B or out.shape[2] != no or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"tta_merge: out must be a contiguous float32 CUDA tensor [{B}, n, {no}]")
+    mask = sum(1 << v for v, f in enumerate(flips) if f)
+    st = _lib.load().cft_tta_merge(preds[0].data_ptr(), preds[1].data_ptr(), preds[2].data_ptr(), B, n[0], n[1], n[2], no, float(scales[0]),
+                                   float(scales[1]), float(scales[2]), mask, float(img_w), out.data_ptr(), out.shape[1], _stream())
+    _lib.check(st, "cft_tta_merge")
+    return out
+
+
 # ------------------------------------------------------------------------------ training-mode forward
 _dropout_state = {"seed": 0x5EED, "calls": 0}
 

@@ -1,6 +1,7 @@
-"""``ModelEMA`` of the reference (``utils/torch_utils.py:269-303``) with the update as ONE HIP launch (``csrc/optim.hip``), and the
+"""``intersect_dicts`` / ``load_pretrained`` (the weight transfer of the reference's train.py:514-525), ``ModelEMA`` of the reference (``utils/torch_utils.py:269-303``) with the update as ONE HIP launch (``csrc/optim.hip``), and the
 copy of a model that such an average - and a checkpoint - needs: parameters, buffers and attributes, not kernel-side caches."""
 import ctypes
+import logging
 import math
 from copy import deepcopy
 
@@ -9,6 +10,8 @@ import torch
 
 from ..models.common import invalidate_packed
 from .optim import CHUNK, DeviceTable, _check_tensor, _one_device
+
+logger = logging.getLogger(__name__)
 
 _DEVICE_ERRORS = ("ModelEMA: the model is on {}; this package runs on the GPU only", "ModelEMA: tensors on {} and {}")
 
@@ -51,6 +54,35 @@ def detached_copy(model):
             dst.__dict__["_graphs"] = {}
     invalidate_packed(copy)
     return copy
+
+
+def intersect_dicts(da, db, exclude=()):
+    """The entries of ``da`` whose key is in ``db`` with the same shape and holds none of the ``exclude`` substrings (the values are
+    ``da``'s): the reference's helper of the same name (utils/torch_utils.py:139-141)."""
+    return {k: v for k, v in da.items() if k in db and v.shape == db[k].shape and not any(x in k for x in exclude)}
+
+
+def load_pretrained(model, ckpt_or_path, exclude=('anchor',)):
+    """Start ``model`` - two-stream or single-stream - from pretrained weights, the statements of the reference's train.py:514-525:
+    the checkpoint's model in fp32, its state dict intersected with the target's by key and shape (``exclude``: train.py leaves the
+    anchors out when the target comes from a cfg), loaded non-strictly.  ``ckpt_or_path``: a checkpoint file (a single-stream
+    ``yolov5*.pt`` un-pickles through ``compat.install_reference_aliases``), the loaded dict, a model, or a state dict.  Returns the
+    list of transferred keys; packed weights and captured graphs of ``model`` are dropped (``invalidate_packed``)."""
+    ckpt = ckpt_or_path
+    if isinstance(ckpt, (str, bytes)) or hasattr(ckpt, "__fspath__"):
+        from ..compat import install_reference_aliases
+        install_reference_aliases()
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
+    if isinstance(ckpt, dict) and isinstance(ckpt.get("model"), torch.nn.Module):
+        ckpt = ckpt["model"]
+    if isinstance(ckpt, torch.nn.Module):
+        ckpt = {k: (v.float() if v.is_floating_point() else v) for k, v in ckpt.state_dict().items()}      # train.py:521 .float()
+    target = de_parallel(model)
+    state = intersect_dicts(ckpt, target.state_dict(), exclude=tuple(exclude))
+    target.load_state_dict(state, strict=False)
+    invalidate_packed(target)
+    logger.info('Transferred %g/%g items' % (len(state), len(target.state_dict())))
+    return list(state)
 
 
 class ModelEMA:

@@ -1,13 +1,17 @@
 """Validate a checkpoint on a paired RGB + IR dataset on disk: the command-line form of the reference's test.py.
 
     python tools/val.py DATA.yaml WEIGHTS.pt [--img-size 640] [--batch-size 32] [--single-cls] [--save-txt] [--save-json] [--plots] [--curves] [--verbose]
+                        [--modality rgb|ir] [--augment]
 
 DATA.yaml holds ``val_rgb`` and ``val_ir`` (directories or *.txt lists; relative paths are taken from the yaml's directory), ``nc``
 and ``names``.  The loader is built as test.py builds it (:86-94: ``rect=True, pad=0.5``, the model's largest stride), every batch is
 one cft_pair_batch_u8 launch, ``evaluate`` does the rest on the GPU, and the table printed is test.py's (:100, :239-245).
 Every label class must be below ``nc`` unless ``--single-cls`` is given (test.py asserts the same of its data yaml); the check runs
 before the first batch.  ``--seeded CFG`` validates a seeded ``models/configs.py`` network instead of a checkpoint: a run without
-weights, e.g. on tests/golden/dataset/data.yaml, whose labels hold a class >= nc on purpose and so need ``--single-cls``."""
+weights, e.g. on tests/golden/dataset/data.yaml, whose labels hold a class >= nc on purpose and so need ``--single-cls``.
+A single-stream checkpoint (``models.yolo.Model``: a YOLOv5-RGB or YOLOv5-IR baseline) is validated on the same paired data with
+``--modality rgb`` or ``--modality ir``; ``--augment`` is test.py's flag, test-time augmentation, for such a model (``--seeded`` takes
+the stock names yolov5s / m / l / x too)."""
 import argparse
 import os
 import sys
@@ -40,6 +44,8 @@ def main(argv=None):
     ap.add_argument("--save-dir", default="runs/val")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--modality", choices=("rgb", "ir"), help="single-stream model: the stream of each pair it sees")
+    ap.add_argument("--augment", action="store_true", help="single-stream model: test-time augmentation (test.py --augment)")
     opt = ap.parse_args(argv)
     if (opt.weights is None) == (opt.seeded is None):
         ap.error("give WEIGHTS or --seeded CFG")
@@ -52,15 +58,24 @@ def main(argv=None):
 
     device = torch.device("cuda:0")
     if opt.seeded:
-        from msod_amd.models.configs import named_config
-        from msod_amd.models.yolo_test import Model
+        from msod_amd.models.configs import STOCK_YAMLS, named_config, stock_config
         from msod_amd.utils.seeded import seeded_state_dict
-        model = Model(named_config(opt.seeded))
+        if opt.seeded in STOCK_YAMLS:
+            from msod_amd.models.yolo import Model
+            model = Model(stock_config(opt.seeded, nc=nc))
+        else:
+            from msod_amd.models.yolo_test import Model
+            model = Model(named_config(opt.seeded))
         model.load_state_dict(seeded_state_dict(model.state_dict(), seed=7))
     else:
         from msod_amd import compat
         model = compat.attempt_load(opt.weights, map_location="cpu")
     model = model.to(device).eval()
+    single = getattr(model, "inputs", 2) == 1
+    if single and opt.modality is None:
+        ap.error("a single-stream model needs --modality rgb or --modality ir")
+    if not single and opt.modality:
+        ap.error("--modality is for single-stream models; a two-stream model takes both streams")
     gs = max(int(model.stride.max()), 32)  # grid size (max stride)
     names = data.get("names") or [str(i) for i in range(nc)]
 
@@ -75,7 +90,8 @@ def main(argv=None):
     details = {}
     evaluate(model, loader, nc, conf_thres=opt.conf_thres, iou_thres=opt.iou_thres, single_cls=opt.single_cls, save_txt=opt.save_txt,
              save_json=opt.save_json, save_dir=opt.save_dir if (opt.save_txt or opt.save_json or opt.plots or opt.curves) else None,
-             details=details, plots=opt.plots, names=names if (opt.plots or opt.curves) else None, device_jpeg=opt.device_jpeg, curves=opt.curves)
+             details=details, plots=opt.plots, names=names if (opt.plots or opt.curves) else None, device_jpeg=opt.device_jpeg, curves=opt.curves,
+             modality=opt.modality, augment=opt.augment)
     res = details["result"]
     cv = details.get("curves")
     lamr = {int(c): v for c, v in zip(cv.ap_class, cv.lamr)} if cv is not None else {}
