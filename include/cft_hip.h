@@ -127,9 +127,26 @@ int cft_bottleneck(const void* x, int ldx, int xoff, const void* w1, int kpad1, 
  * every row in the order the kernel keeps it in LDS (c * kpad2 * 2 bytes, the size of w2). */
 int cft_bottleneck_pack_w2(const void* w2, int kpad2, int c, void* w2_stages, int dtype, void* stream);
 
-/* Tuning knob: force one tile configuration of cft_conv2d (0 = automatic, the default; see
- * csrc/conv_gemm.hip for the table).  The setting is PER HOST THREAD (thread_local): it reaches the launches the calling
- * thread issues and no other's.  Returns the previous value.  Not needed for normal use. */
+/* Tuning knob (A/B timing, tests): force how cft_conv2d and its relatives pick a kernel.  The ids:
+ *   CFT_CONV_AUTO (0)              the automatic choice, the default;
+ *   CFT_CONV_REGISTER_STAGED (1)   the register-staged 128 x 128 tile (no LDS-DMA);
+ *   2, 4, 6, 7, 8, 23, 27, 30, 32, 33, 51, 60, 63, 70 - 75
+ *                                  one forced tile each (the CONV_TILE_VARIANTS list of csrc/conv_gemm.hip);
+ *   CFT_CONV_ASM (96)              the hand-scheduled 8-wave kernel wherever a layer is eligible, in 256-row tiles;
+ *   CFT_CONV_ASM_TILE + 1 ... 4    the same in 224 / 208 / 192 / 128-row tiles (only the automatic choice picks a height by tile count);
+ *   CFT_CONV_ROUND5 (97)           the automatic choice without the hand-scheduled kernels (plain and chained);
+ *   CFT_CONV_GENERIC_WALK (900)    the automatic tiles on the generic address path instead of the uniform K walk.
+ * The setting is PER HOST THREAD (thread_local): it reaches the launches the calling thread issues and no other's.
+ * Returns the previous value (>= 0).  Any other id is refused: the setting stays as it was, cft_last_error names the id and
+ * the call returns -1.  Not needed for normal use. */
+enum {
+  CFT_CONV_AUTO = 0,
+  CFT_CONV_REGISTER_STAGED = 1,
+  CFT_CONV_ASM = 96,
+  CFT_CONV_ASM_TILE = 960,
+  CFT_CONV_ROUND5 = 97,
+  CFT_CONV_GENERIC_WALK = 900
+};
 int cft_set_conv_variant(int variant);
 
 /*

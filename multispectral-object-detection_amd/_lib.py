@@ -14,7 +14,7 @@ import subprocess
 import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: experiments with an alternative build, e.g. the probe library)
+LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: load another build of the library, e.g. one made with tools/build.sh and CFT_OUT)
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "curves.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip", "jpeg_encode.hip", "tta.hip")
 

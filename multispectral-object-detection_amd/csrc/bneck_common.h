@@ -1,4 +1,4 @@
-// Launch parameters of the fused Bottleneck kernels (bottleneck.hip, bottleneck_asm.hip).
+// Launch parameters of the fused Bottleneck kernels (bottleneck.hip).
 #pragma once
 #include "cft_common.h"
 
@@ -26,8 +26,3 @@ __device__ __forceinline__ int bneck_divmod(int n, int d, uint32_t m, int& rem) 
   rem = r;
   return q;
 }
-
-// bottleneck_asm.hip: the 128-channel Bottleneck on 16 x 16-pixel tiles with the hand-scheduled 3x3 loop (dtype CFT_BF16 / CFT_F16)
-int bneck128_asm_launch(const Bneck128Params& p, int dtype, hipStream_t stream);
-// probes/bottleneck_r6.hip: the round-6 form of the two product kernels (c = 64 / 128), for A/B timing in the probe build
-int bneck_r6_launch(const Bneck128Params& p, int c, int dtype, hipStream_t stream);

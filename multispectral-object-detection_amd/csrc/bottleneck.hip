@@ -24,14 +24,8 @@
 //     and their t values are written as zeros by the few lanes that own them instead of being masked in every lane;
 //   * the patch addresses of the 3x3 loop - 4 rows x 3 columns per lane - are formed once per tile; a step adds immediates
 //     (plane) or flips one bit (k half) and the tap loop is unrolled, so its first step needs no zero fragments.
-// ABL template arguments are timing probes (results wrong): compiled only with -DCFT_PROBES (tools/build_probes.sh), which also
-// keeps the kernels as they were before that diet (probes/bottleneck_r6.hip, variant 95) for A/B timing.
 #include "cft_common.h"
 #include <stdlib.h>
-
-#ifdef CFT_PROBES
-extern thread_local int g_conv_variant;   // conv_gemm.hip (cft_set_conv_variant)
-#endif
 
 __device__ __attribute__((aligned(16))) uint32_t cft_zero_page_b[4] = {0u, 0u, 0u, 0u};
 // 256 zero bytes: what a lane whose halo pixel lies outside the image requests instead of x (16 bytes at 0, 64, 128, 192)
@@ -55,7 +49,7 @@ typedef const __attribute__((address_space(1))) void gbl_void_t;
 //   * the patch's 12 row tiles are split evenly: wave w owns row tile w in both output-channel passes of the W1 stage and
 //     row tile 8 + w / 2 in ONE of them (the two waves of a SIMD in different ones): 8 x requests per lane for every wave;
 //   * wave (wmr, wnc) owns tile rows 2 wmr, 2 wmr + 1 x 64 channels; biases live in the 12 spare rows of plane 1 of the patch.
-template <typename T, int ABL = 0>
+template <typename T>
 __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Params p) {
   constexpr int C = 128, TH = 8, TW = 16, PW = TW + 2, PH = TH + 2, NPIX = PW * PH;   // 180 patch pixels
   constexpr int NRT = (NPIX + 15) / 16;                             // 12 row tiles of the patch
@@ -63,7 +57,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
   constexpr int SLOT = 8192;
   constexpr int SLD = 64 + 4;
   constexpr int RW = 2;
-  constexpr int XS = (ABL & 4) ? 0 : 2 * RW;                        // shortcut requests per lane
+  constexpr int XS = 2 * RW;                                        // shortcut requests per lane
   static_assert(PW == 18 && NRT == 12, "the mul-shift below divides by 18; 8 + 4 row tiles");
   extern __shared__ __attribute__((aligned(128))) unsigned char smem[];   // 128: the k-half flip below is an XOR on absolute patch addresses
   unsigned char* sT = smem;
@@ -94,8 +88,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
     uint32_t& so_ = ss_ < 4 ? so1 : so2;                                                                 \
     asm("" : "+s"(ub_), "+v"(so_));                       /* scalar base + 32-bit lane offset, widened HERE: the request's own address mode, no 64-bit vector add */ \
     const unsigned char* src_ = ub_ + so_;                                                               \
-    if constexpr (!(ABL & 8))                                                                            \
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)src_, (lds_void_t*)(sR + (ss_ & 3) * SLOT + wave * 1024), 16, 0, 0); \
+    __builtin_amdgcn_global_load_lds((gbl_void_t*)src_, (lds_void_t*)(sR + (ss_ & 3) * SLOT + wave * 1024), 16, 0, 0); \
   }
 #define BNC_SYNC(n_)                                                                                     \
   {                                                                                                      \
@@ -132,10 +125,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
       const uint32_t xo = ((uint32_t)((brow + gy) * p.W + gx) * (uint32_t)p.ldx + (uint32_t)(p.xoff + lgrp * 8)) * 2;
       const unsigned char* xp = keep[it] ? p.x + xo : reinterpret_cast<const unsigned char*>(cft_bneck_zero_row);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        if constexpr (ABL & 256) a1n[it][ks] = gran_t{0x3c003c00u + (unsigned)lane, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};   // probe: no x requests
-        else a1n[it][ks] = *reinterpret_cast<const gran_t*>(xp + ks * 64);
-      }
+      for (int ks = 0; ks < 4; ++ks) a1n[it][ks] = *reinterpret_cast<const gran_t*>(xp + ks * 64);
     }
     __builtin_amdgcn_sched_barrier(0);
     BNC_STAGE(0)
@@ -171,17 +161,15 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
           wf[j][0] = *reinterpret_cast<const gran_t*>(sR + (s & 3) * SLOT + j * 2048 + fb);
           wf[j][1] = *reinterpret_cast<const gran_t*>(sR + (s & 3) * SLOT + j * 2048 + (fb ^ 64));
         }
-        if constexpr (!(ABL & 1)) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc1[0][j] = mma_granule<T>(wf[j][ks], a1n[0][kt * 2 + ks], acc1[0][j]);
+        if (hp_t == jh) {
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc1[0][j] = mma_granule<T>(wf[j][ks], a1n[0][kt * 2 + ks], acc1[0][j]);
-          if (hp_t == jh) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) acc1[1][j] = mma_granule<T>(wf[j][ks], a1n[1][kt * 2 + ks], acc1[1][j]);
-          }
+            for (int j = 0; j < 4; ++j) acc1[1][j] = mma_granule<T>(wf[j][ks], a1n[1][kt * 2 + ks], acc1[1][j]);
         }
         BNC_SYNC(2)                                      // stage s + 1 landed (s + 2, s + 3 in flight); this slot's reads retired
       }
@@ -197,7 +185,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
               const f32x4_t b1q = *reinterpret_cast<const f32x4_t*>(sB + jh * 64 + cc);
               float v[4];
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = (ABL & 1) ? 0.0f : apply_act<(ABL & 512) ? CFT_ACT_NONE : CFT_ACT_SILU>(acc1[it][j][e] + b1q[e]);
+              for (int e = 0; e < 4; ++e) v[e] = apply_act<CFT_ACT_SILU>(acc1[it][j][e] + b1q[e]);
               uint2 w;
               w.x = Elem<T>::pack2(v[0], v[1]);
               w.y = Elem<T>::pack2(v[2], v[3]);
@@ -253,10 +241,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
 #define BNC_MMA(set_)                                                                                    \
     {                                                                                                    \
       _Pragma("unroll") for (int i = 0; i < RW; ++i)                                                     \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                  \
-          if constexpr (ABL & 2) { asm volatile("" ::"v"(af[set_][i]), "v"(bf[set_][j])); }              \
-          else acc[i][j] = mma_granule<T>(af[set_][i], bf[set_][j], acc[i][j]);                          \
-        }                                                                                                \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = mma_granule<T>(af[set_][i], bf[set_][j], acc[i][j]); \
       __builtin_amdgcn_sched_barrier(0);                                                                 \
     }
     // shortcut pixels and output pixels: lane -> (pixel row of the strip, 8 channels), two pixels per lane and strip
@@ -267,10 +252,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
       const uint32_t rowo = (uint32_t)((brow + min(y0 + wmr * RW + i, p.H - 1)) * p.W) * (uint32_t)p.ldx + (uint32_t)(p.xoff + wnc * 64); \
       _Pragma("unroll") for (int v = 0; v < 2; ++v) {                                                    \
         const int x = min(x0 + erow + v * 8, p.W - 1);                                                   \
-        if constexpr (XS != 0)                                                                           \
-          rs[i][v] = *reinterpret_cast<const gran_t*>(p.x + ((uint32_t)x * (uint32_t)p.ldx + rowo + (uint32_t)ecol) * 2); \
-        else                                                                                             \
-          rs[i][v] = gran_t{0u, 0u, 0u, 0u};                                                             \
+        rs[i][v] = *reinterpret_cast<const gran_t*>(p.x + ((uint32_t)x * (uint32_t)p.ldx + rowo + (uint32_t)ecol) * 2); \
       }                                                                                                  \
     }                                                                                                    \
     __builtin_amdgcn_sched_barrier(0);
@@ -301,12 +283,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
 
     // [census: epilogue]
     // ---- epilogue: strip i = tile row 2 wmr + i, 16 pixels x 64 channels
-    if constexpr (ABL & 4) {
-#pragma unroll
-      for (int i = 0; i < RW; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    } else {
+    {
       float b2v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) b2v[j] = sB[C + wnc * 64 + j * 16 + lrow];
@@ -319,7 +296,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            stage[(lgrp * 4 + e) * SLD + j * 16 + lrow] = apply_act<(ABL & 512) ? CFT_ACT_NONE : CFT_ACT_SILU>(acc[i][j][e] + b2v[j]);
+            stage[(lgrp * 4 + e) * SLD + j * 16 + lrow] = apply_act<CFT_ACT_SILU>(acc[i][j][e] + b2v[j]);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -359,7 +336,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck128c_kernel(const Bneck128Pa
 // ring three stages ahead.  42 + 32 KiB: two workgroups per CU (a weights-resident form, 117 KiB, had
 // one whose 16 waves ran their SiLU passes and their MFMAs in lock step).  Wave w owns tile rows 2 w, 2 w + 1 and all 64
 // channels; per tap it reads 4 + 8 fragments for 16 MFMAs, the second k half under the MFMAs of the first.
-template <typename T, int ABL = 0>
+template <typename T>
 __global__ void __launch_bounds__(512, 4) bottleneck64r_kernel(const Bneck128Params p) {
   constexpr int C = 64, TS = 16, PW = TS + 2, NPIX = PW * PW;       // 324 patch pixels
   constexpr int NRT = (NPIX + 15) / 16;                             // 21 row tiles of the patch
@@ -402,8 +379,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck64r_kernel(const Bneck128Par
     uint32_t& so_ = ss_ == 0 ? so1 : so2;                                                                \
     asm("" : "+s"(ub_), "+v"(so_));                       /* scalar base + 32-bit lane offset, widened HERE: the request's own address mode, no 64-bit vector add */ \
     const unsigned char* src_ = ub_ + so_;                                                               \
-    if constexpr (!(ABL & 8))                                                                            \
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)src_, (lds_void_t*)(sR + (ss_ & 3) * SLOT + wave * 1024), 16, 0, 0); \
+    __builtin_amdgcn_global_load_lds((gbl_void_t*)src_, (lds_void_t*)(sR + (ss_ & 3) * SLOT + wave * 1024), 16, 0, 0); \
   }
 #define BNR_SYNC(n_)                                                                                     \
   {                                                                                                      \
@@ -461,16 +437,14 @@ __global__ void __launch_bounds__(512, 4) bottleneck64r_kernel(const Bneck128Par
       wf[j][0] = *reinterpret_cast<const gran_t*>(sR + j * 2048 + fb);
       wf[j][1] = *reinterpret_cast<const gran_t*>(sR + j * 2048 + (fb ^ 64));
     }
-    if constexpr (!(ABL & 1)) {
 #pragma unroll
-      for (int it = 0; it < RT1; ++it)
-        if (wave + 8 * it < NRT) {
+    for (int it = 0; it < RT1; ++it)
+      if (wave + 8 * it < NRT) {
 #pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc1[it][j] = mma_granule<T>(wf[j][ks], a1[it][ks], acc1[it][j]);
-        }
-    }
+          for (int j = 0; j < 4; ++j) acc1[it][j] = mma_granule<T>(wf[j][ks], a1[it][ks], acc1[it][j]);
+      }
     BNR_SYNC(2)                                          // stage 1 landed (2, 3 in flight); slot 0's reads retired
     // [census: patch write]
     // the lane's 4 channels of output-channel group j sit at tb ^ (j << 5): 16 j + 4 lgrp is granule 2 j + (lgrp >> 1), half lgrp & 1
@@ -486,7 +460,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck64r_kernel(const Bneck128Par
             const f32x4_t b1q = *reinterpret_cast<const f32x4_t*>(sB + cc);
             float v[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (ABL & 1) ? 0.0f : apply_act<CFT_ACT_SILU>(acc1[it][j][e] + b1q[e]);
+            for (int e = 0; e < 4; ++e) v[e] = apply_act<CFT_ACT_SILU>(acc1[it][j][e] + b1q[e]);
             uint2 w;
             w.x = Elem<T>::pack2(v[0], v[1]);
             w.y = Elem<T>::pack2(v[2], v[3]);
@@ -529,10 +503,7 @@ __global__ void __launch_bounds__(512, 4) bottleneck64r_kernel(const Bneck128Par
 #define BNR_MMA(set_)                                                                                    \
   {                                                                                                      \
     _Pragma("unroll") for (int i = 0; i < RW; ++i)                                                       \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                    \
-        if constexpr (ABL & 2) { asm volatile("" ::"v"(af[set_][i]), "v"(bf[set_][j])); }                \
-        else acc[i][j] = mma_granule<T>(af[set_][i], bf[set_][j], acc[i][j]);                            \
-      }                                                                                                  \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = mma_granule<T>(af[set_][i], bf[set_][j], acc[i][j]); \
     __builtin_amdgcn_sched_barrier(0);                                                                   \
   }
 #pragma unroll
@@ -557,13 +528,6 @@ __global__ void __launch_bounds__(512, 4) bottleneck64r_kernel(const Bneck128Par
 
   // [census: epilogue]
   // ---- epilogue: strip i = tile row 2 wave + i, 16 pixels x 64 channels
-  if constexpr (ABL & 4) {
-#pragma unroll
-    for (int i = 0; i < RW; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
   float b2v[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) b2v[j] = sB[C + j * 16 + lrow];
@@ -682,50 +646,23 @@ extern "C" int cft_bottleneck(const void* x, int ldx, int xoff, const void* w1, 
   q.m_tiles = bneck_magic(q.tiles_x * q.tiles_y); q.m_tiles_x = bneck_magic(q.tiles_x);
   hipStream_t s_ = as_stream(stream);
   const dim3 grid(q.ntiles);
-#ifdef CFT_PROBES
-  if (g_conv_variant == 95) return bneck_r6_launch(q, c, dtype, s_);   // the kernels before the instruction diet (probes/bottleneck_r6.hip): A/B only
-#endif
-#define BNC_LAUNCH(T_, ABL_)                                                                          \
+#define BNC_LAUNCH(T_)                                                                                \
   {                                                                                                   \
     constexpr int smem_ = 2 * 12 * 16 * 128 + 2 * 16384;                                              \
-    cft_allow_lds<&bottleneck128c_kernel<T_, ABL_>>(smem_);                                           \
-    hipLaunchKernelGGL((bottleneck128c_kernel<T_, ABL_>), grid, dim3(512), smem_, s_, q);             \
+    cft_allow_lds<&bottleneck128c_kernel<T_>>(smem_);                                                 \
+    hipLaunchKernelGGL((bottleneck128c_kernel<T_>), grid, dim3(512), smem_, s_, q);                   \
   }
-#define BNR_LAUNCH(T_, ABL_)                                                                          \
+#define BNR_LAUNCH(T_)                                                                                \
   {                                                                                                   \
     constexpr int smem_ = 21 * 16 * 128 + 4 * 8192;                                                   \
-    cft_allow_lds<&bottleneck64r_kernel<T_, ABL_>>(smem_);                                            \
-    hipLaunchKernelGGL((bottleneck64r_kernel<T_, ABL_>), grid, dim3(512), smem_, s_, q);              \
+    cft_allow_lds<&bottleneck64r_kernel<T_>>(smem_);                                                  \
+    hipLaunchKernelGGL((bottleneck64r_kernel<T_>), grid, dim3(512), smem_, s_, q);                    \
   }
-#ifdef CFT_PROBES   // timing probes (results wrong): no W1-stage MFMAs / no 3x3 MFMAs / no epilogue / no weight DMA / no x requests / no SiLU
-  if (dtype == CFT_BF16) {
-    switch (g_conv_variant) {
-      case 9201: if (c == 128) { BNC_LAUNCH(uint16_t, 1) return cft_check_launch("bottleneck128c_kernel(probe)"); } break;
-      case 9202: if (c == 128) { BNC_LAUNCH(uint16_t, 2) return cft_check_launch("bottleneck128c_kernel(probe)"); } break;
-      case 9204: if (c == 128) { BNC_LAUNCH(uint16_t, 4) return cft_check_launch("bottleneck128c_kernel(probe)"); } break;
-      case 9208: if (c == 128) { BNC_LAUNCH(uint16_t, 8) return cft_check_launch("bottleneck128c_kernel(probe)"); } break;
-      case 9456: if (c == 128) { BNC_LAUNCH(uint16_t, 256) return cft_check_launch("bottleneck128c_kernel(probe)"); } break;
-      case 9712: if (c == 128) { BNC_LAUNCH(uint16_t, 512) return cft_check_launch("bottleneck128c_kernel(probe)"); } break;
-      case 9601: if (c == 64) { BNR_LAUNCH(uint16_t, 1) return cft_check_launch("bottleneck64r_kernel(probe)"); } break;
-      case 9602: if (c == 64) { BNR_LAUNCH(uint16_t, 2) return cft_check_launch("bottleneck64r_kernel(probe)"); } break;
-      case 9604: if (c == 64) { BNR_LAUNCH(uint16_t, 4) return cft_check_launch("bottleneck64r_kernel(probe)"); } break;
-      case 9608: if (c == 64) { BNR_LAUNCH(uint16_t, 8) return cft_check_launch("bottleneck64r_kernel(probe)"); } break;
-      default: break;
-    }
-  }
-#endif
   if (c == 128) {
-#ifdef CFT_PROBES
-    if (g_conv_variant == 98 || (g_conv_variant >= 9300 && g_conv_variant < 9400)) {   // the 16 x 16-tile kernel with the hand-scheduled 3x3 loop (probes/bottleneck_asm.hip: slower, A/B only)
-      q.tiles_y = (H + 15) / 16;
-      q.ntiles = B * q.tiles_x * q.tiles_y;
-      return bneck128_asm_launch(q, dtype, s_);
-    }
-#endif
-    if (dtype == CFT_F16) BNC_LAUNCH(f16_t, 0) else BNC_LAUNCH(uint16_t, 0)
+    if (dtype == CFT_F16) BNC_LAUNCH(f16_t) else BNC_LAUNCH(uint16_t)
     return cft_check_launch("bottleneck128c_kernel");
   }
-  if (dtype == CFT_F16) BNR_LAUNCH(f16_t, 0) else BNR_LAUNCH(uint16_t, 0)
+  if (dtype == CFT_F16) BNR_LAUNCH(f16_t) else BNR_LAUNCH(uint16_t)
 #undef BNC_LAUNCH
 #undef BNR_LAUNCH
   return cft_check_launch("bottleneck64r_kernel");

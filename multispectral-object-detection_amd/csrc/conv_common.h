@@ -1,4 +1,4 @@
-// Shared pieces of the implicit-GEMM kernels (conv_gemm.hip, conv_ring.hip): launch parameters, the zero page / zero region that
+// Shared pieces of the implicit-GEMM kernels (conv_gemm.hip, conv_gemm_asm.hip): launch parameters, the zero page / zero region that
 // masked granules fetch from (one copy per translation unit: device code is linked per file), the fused epilogue.
 #pragma once
 #include "cft_common.h"
@@ -183,6 +183,3 @@ int conv_asm_tile_rows(int tile);
 int conv_asm_launch(const ConvParams& p, int dtype, int tile, hipStream_t stream);
 bool conv_asm_chain_ok(const ConvParams& p, int dtype);   // the chained pair with a 256-channel first layer (p.w2 / bias2 / N2 [/ res / y1] set)
 int conv_asm_chain_launch(const ConvParams& p, int dtype, hipStream_t stream);
-
-// conv_ring.hip: launch the ring kernel (dtype CFT_BF16 / CFT_F16; ablate: timing probes of -DCFT_PROBES builds, 0 otherwise)
-int conv_ring_launch(const ConvParams& p, int dtype, int ablate, hipStream_t stream);

@@ -32,8 +32,6 @@
 // image rows) run on the same XCD and hit the same 4 MiB L2.
 #include "conv_common.h"
 
-// ABLATE (tuning only, bit mask): 1 = no global loads after the first tile (compute-only bound); 2 = no MFMA
-// (staging-only bound); 16 = no epilogue (no bias/activation/residual/stores).
 // UNIK (uniform K walk; needs GLDS, Cin % K-step == 0, Kpad == K): every thread of the workgroup is at the same (tap, channel
 // chunk) in a K step, so the walk over taps / chunks is SCALAR (SGPR) arithmetic and a thread only keeps constant pointers:
 // the staging block shrinks from ~80 to ~25 instructions per K step (16 waves issue it in lock step after every barrier,
@@ -49,7 +47,7 @@
 // image layout, every lane adds "its" dwords in fp32 and writes the rounded sum back in place, and the finished images are stored to y1
 // granule by granule (32 KiB right before each MFMA step of the second GEMM, drained at the barrier behind it).
 // split-K (p.ksplit > 1, pointwise layers on the uniform K walk): see ConvParams.
-template <typename T, int BM, int BN, int WGM, int WGN, bool GLDS, int ABLATE = 0, bool UNIK = false, bool CHAIN = false, bool CRES = false>
+template <typename T, int BM, int BN, int WGM, int WGN, bool GLDS, bool UNIK = false, bool CHAIN = false, bool CRES = false>
 __global__ void __launch_bounds__(64 * WGM * WGN) conv_gemm_kernel(const ConvParams p) {
   constexpr int NTHR = 64 * WGM * WGN;
   constexpr int GE = Elem<T>::GE;
@@ -118,7 +116,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_gemm_kernel(const ConvPar
   // later (working set per XCD: 32 CUs x 43 KB) instead of Cin / 64 steps later (32 x 172 KB for Cin = 256 - more than the
   // 4 MiB L2, PMC: 77 % hit rate, 1.8 x the algorithmic HBM reads, and every K step waits for a miss).  Same products,
   // another summation order: results differ from the tap-major walk in the last bits (all tile variants walk alike).
-  const bool chunk_major = (ABLATE & 64) ? false : (p.KS == 3 && p.Cin >= 4 * BK && p.Cin % BK == 0 && p.K == 9 * p.Cin);
+  const bool chunk_major = p.KS == 3 && p.Cin >= 4 * BK && p.Cin % BK == 0 && p.K == 9 * p.Cin;
   int kglob = g * GE;                  // this thread's k position (column of the packed weights)
 
   gran_t ra[GLDS ? 1 : A_PER], rb[GLDS ? 1 : B_PER];
@@ -258,10 +256,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_gemm_kernel(const ConvPar
       bf[j] = *reinterpret_cast<const gran_t*>((bbase_) + row * 128 + ((kg ^ (row & 7)) << 4));         \
     }                                                                                                  \
     _Pragma("unroll") for (int i = 0; i < MT; ++i)                                                     \
-      _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                                 \
-        if constexpr (ABLATE & 2) { asm volatile("" ::"v"(af[i]), "v"(bf[j])); }                       \
-        else acc[i][j] = mma_granule<T>(af[i], bf[j], acc[i][j]);                                      \
-      }                                                                                                \
+      _Pragma("unroll") for (int j = 0; j < NT; ++j) acc[i][j] = mma_granule<T>(af[i], bf[j], acc[i][j]); \
   }
 
   f32x4_t acc[MT][NT];
@@ -270,7 +265,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_gemm_kernel(const ConvPar
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float bias_v[NT];
-  if constexpr (!(ABLATE & 32)) conv_load_bias<WN>(p, n0, wn, lane, bias_v);
+  conv_load_bias<WN>(p, n0, wn, lane, bias_v);
 
   const int nk = (UNIK && p.ksplit > 1) ? p.ksteps : p.Kpad / BK;
   if constexpr (UNIK) { CFT_LOAD_TILE_U(0) } else { CFT_LOAD_TILE(0, 0) }
@@ -279,7 +274,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_gemm_kernel(const ConvPar
   const int lrow = lane & 15, lgrp = lane >> 4;
   for (int kt = 0; kt < nk; ++kt) {
     const int buf = kt & 1;
-    if (kt + 1 < nk && !(ABLATE & 1)) {
+    if (kt + 1 < nk) {
       if constexpr (UNIK) { CFT_LOAD_TILE_U(buf ^ 1) } else { CFT_LOAD_TILE(kt + 1, buf ^ 1) }
     }
     CFT_COMPUTE_STEP(buf)
@@ -433,14 +428,6 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_gemm_kernel(const ConvPar
     conv_epilogue<TH, WM, WN>(p2, acc, smem, m0, 0, wm, wn, wave, lane, bias2_v);
     return;
   }
-  if constexpr (ABLATE & 16) {   // timing probe: no epilogue (keep the accumulators alive)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
-  if constexpr (ABLATE & 32) conv_load_bias<WN>(p, n0, wn, lane, bias_v);   // A/B probe: the round-1 placement
   if (p.ksplit > 1) {                    // uniform: fp32 partial sums of this split (host: out_f32, no activation, no residual)
     ConvParams ps = p;
     ps.y = p.y + (long)split * p.M * p.ldy * 4;
@@ -466,23 +453,52 @@ static void set_magic(int d, uint32_t& mul, uint32_t& sh) {
 }
 
 
-// Tile variants.  0 = automatic choice; the others force one configuration (tuning / A-B tests).
+// cft_set_conv_variant (tuning / A-B tests; the ids are listed at its prototype in include/cft_hip.h): CFT_CONV_AUTO = the automatic
+// choice, the named CFT_CONV_* ids, and the forced tiles below - X(id, BM, BN, WGM, WGN), each on the uniform K walk where the
+// layer allows it.  dispatch_conv's switch and conv_variant_known both expand from this one list.
+#define CONV_TILE_VARIANTS(X)                                                                          \
+  X(2, 128, 128, 2, 2) X(4, 128, 64, 2, 2) X(6, 256, 64, 4, 2) X(7, 64, 128, 2, 2) X(8, 64, 64, 2, 2)    \
+  X(23, 128, 128, 2, 4) X(27, 256, 256, 4, 4) X(30, 512, 128, 8, 2) X(32, 512, 64, 8, 2) X(33, 256, 128, 4, 2) \
+  X(51, 192, 128, 2, 4) X(60, 128, 256, 4, 4) X(63, 64, 128, 2, 4)                                      \
+  /* 80/160-wide tiles: yolov5x / yolov5m channel counts */                                            \
+  X(70, 256, 160, 8, 2) X(71, 256, 160, 4, 2) X(72, 128, 160, 4, 2) X(73, 256, 80, 4, 1) X(74, 256, 80, 8, 1) X(75, 128, 80, 4, 1)
+
+// the asm kernel at tile index 0 (CFT_CONV_ASM) or t (CFT_CONV_ASM_TILE + t) of conv_gemm_asm.hip's tile heights
+#define CONV_ASM_VARIANT_CASES case CFT_CONV_ASM: case CFT_CONV_ASM_TILE + 1: case CFT_CONV_ASM_TILE + 2: case CFT_CONV_ASM_TILE + 3: case CFT_CONV_ASM_TILE + 4:
+static_assert(CONV_ASM_NTILES == 5, "CONV_ASM_VARIANT_CASES names one id per tile height of conv_gemm_asm.hip");
+
+static bool conv_variant_known(int v) {
+  switch (v) {
+    case CFT_CONV_AUTO: case CFT_CONV_REGISTER_STAGED: case CFT_CONV_ROUND5: case CFT_CONV_GENERIC_WALK:
+    CONV_ASM_VARIANT_CASES
+#define X(id, BM, BN, WGM, WGN) case id:
+    CONV_TILE_VARIANTS(X)
+#undef X
+      return true;
+    default: return false;
+  }
+}
+
 // Per host thread (two forwards may be issued from two threads; a test's cft_set_conv_variant must not reach the other's launches).
-thread_local int g_conv_variant = 0;   // also read by bottleneck.hip in probe builds (-DCFT_PROBES)
+static thread_local int g_conv_variant = CFT_CONV_AUTO;
 extern "C" int cft_set_conv_variant(int v) {
+  if (!conv_variant_known(v)) {
+    char buf[96];
+    snprintf(buf, sizeof(buf), "cft_set_conv_variant: unknown variant id %d (the setting is unchanged)", v);
+    cft_set_error(buf);
+    return -1;
+  }
   const int old = g_conv_variant;
   g_conv_variant = v;
   return old;
 }
 
-int cft_set_conv_variant_peek() { return g_conv_variant; }   // (bottleneck.hip: variant 97 = the round-5 kernels)
-
-template <typename T, int BM, int BN, int WGM, int WGN, bool GLDS, int ABLATE = 0, bool UNIK = false, bool CHAIN = false, bool CRES = false>
+template <typename T, int BM, int BN, int WGM, int WGN, bool GLDS, bool UNIK = false, bool CHAIN = false, bool CRES = false>
 static int launch_conv(const ConvParams& p, hipStream_t stream) {
   // (chained kernel with four 64-channel images: they take all of the staging area, the second layer's weights one buffer behind it)
   constexpr int smem_bytes = (CHAIN && BN / 64 > 2) ? (BN / 64) * BM * 128 + BN * 128 : 2 * (BM + BN) * 128;
   static_assert(!CHAIN || (BN / 64) * BM * 128 >= 2 * (BM + BN) * 128 || BN / 64 <= 2, "chained GEMM: LDS map");
-  cft_allow_lds<&conv_gemm_kernel<T, BM, BN, WGM, WGN, GLDS, ABLATE, UNIK, CHAIN, CRES>>(smem_bytes);
+  cft_allow_lds<&conv_gemm_kernel<T, BM, BN, WGM, WGN, GLDS, UNIK, CHAIN, CRES>>(smem_bytes);
   ConvParams q = p;
   const int tilesM = (p.M + BM - 1) / BM;
   q.tilesN = (p.N + BN - 1) / BN;
@@ -491,34 +507,19 @@ static int launch_conv(const ConvParams& p, hipStream_t stream) {
     cft_set_error("conv_gemm_kernel: split-K needs the uniform-K-walk instantiation (this variant forces the generic address path)");
     return CFT_EINVAL;
   }
-  hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, WGM, WGN, GLDS, ABLATE, UNIK, CHAIN, CRES>), dim3(tilesM * q.tilesN * q.ksplit), dim3(64 * WGM * WGN), smem_bytes, stream, q);
+  hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, WGM, WGN, GLDS, UNIK, CHAIN, CRES>), dim3(tilesM * q.tilesN * q.ksplit), dim3(64 * WGM * WGN), smem_bytes, stream, q);
   return cft_check_launch("conv_gemm_kernel");
 }
 
 // Automatic choice: the uniform-K-walk form of a tile configuration whenever the layer allows it (every layer of the CFT
-// networks except the Focus conv and the 80 / 160 / 320-channel layers of yolov5x); variant 900 forces the generic path (A/B).
+// networks except the Focus conv and the 80 / 160 / 320-channel layers of yolov5x); CFT_CONV_GENERIC_WALK forces the generic path (A/B).
 template <typename T, int BM, int BN, int WGM, int WGN>
 static int launch_auto(const ConvParams& p, hipStream_t stream) {
   constexpr int BK = 8 * Elem<T>::GE;
-  const bool unik = g_conv_variant != 900 && p.Cin % BK == 0 && p.Kpad == p.K && 2L * p.Kpad * (long)sizeof(T) + 128 <= CFT_ZERO_REGION_BYTES;
-  if (unik) return launch_conv<T, BM, BN, WGM, WGN, true, 0, true>(p, stream);
+  const bool unik = g_conv_variant != CFT_CONV_GENERIC_WALK && p.Cin % BK == 0 && p.Kpad == p.K && 2L * p.Kpad * (long)sizeof(T) + 128 <= CFT_ZERO_REGION_BYTES;
+  if (unik) return launch_conv<T, BM, BN, WGM, WGN, true, true>(p, stream);
   return launch_conv<T, BM, BN, WGM, WGN, true>(p, stream);
 }
-
-#ifdef CFT_PROBES
-// Eligibility of the ring kernel: 16-bit operands, Cin a multiple of the 64-wide K step (uniform walk), no K padding.
-template <typename T>
-static bool ring_ok(const ConvParams& p) {
-  // (the last clause: masked granules are fetched at the out-of-range buffer offset 2^31, so both buffers must end below it)
-  return sizeof(T) == 2 && p.Cin % 64 == 0 && p.Kpad == p.K && p.KS <= 3 &&
-         p.x_bytes + 2L * ((long)p.W + 1) * p.ldx < (1L << 31) && p.w_bytes < (1L << 31);
-}
-
-template <typename T, int ABLATE = 0>
-static int launch_ring(const ConvParams& p, hipStream_t stream) {
-  return conv_ring_launch(p, sizeof(T) != 2 ? CFT_F32 : (__is_same(T, f16_t) ? CFT_F16 : CFT_BF16), ABLATE, stream);   // conv_ring.hip
-}
-#endif
 
 template <typename T>
 static constexpr int dtype_code() { return sizeof(T) != 2 ? CFT_F32 : (__is_same(T, f16_t) ? CFT_F16 : CFT_BF16); }
@@ -526,43 +527,13 @@ static constexpr int dtype_code() { return sizeof(T) != 2 ? CFT_F32 : (__is_same
 template <typename T>
 static int dispatch_conv(const ConvParams& p, hipStream_t stream) {
   switch (g_conv_variant) {
-    case 96: case 961: case 962: case 963: case 964:   // the hand-scheduled 8-wave kernel wherever eligible, tile heights 256 / 224 / 208 / 192 / 128 (tests)
-      if (conv_asm_ok(p, dtype_code<T>())) return conv_asm_launch(p, dtype_code<T>(), g_conv_variant == 96 ? 0 : g_conv_variant - 960, stream);
+    CONV_ASM_VARIANT_CASES   // the hand-scheduled 8-wave kernel wherever eligible, tile heights 256 / 224 / 208 / 192 / 128 (tests)
+      if (conv_asm_ok(p, dtype_code<T>())) return conv_asm_launch(p, dtype_code<T>(), g_conv_variant == CFT_CONV_ASM ? 0 : g_conv_variant - CFT_CONV_ASM_TILE, stream);
       break;
-    case 1: return launch_conv<T, 128, 128, 2, 2, false>(p, stream);   // register-staged baseline
-    case 2: return launch_auto<T, 128, 128, 2, 2>(p, stream);
-    case 4: return launch_auto<T, 128, 64, 2, 2>(p, stream);
-    case 6: return launch_auto<T, 256, 64, 4, 2>(p, stream);
-    case 7: return launch_auto<T, 64, 128, 2, 2>(p, stream);
-    case 8: return launch_auto<T, 64, 64, 2, 2>(p, stream);
-    case 23: return launch_auto<T, 128, 128, 2, 4>(p, stream);
-    case 27: return launch_auto<T, 256, 256, 4, 4>(p, stream);
-    case 30: return launch_auto<T, 512, 128, 8, 2>(p, stream);
-    case 32: return launch_auto<T, 512, 64, 8, 2>(p, stream);
-    case 33: return launch_auto<T, 256, 128, 4, 2>(p, stream);
-    case 51: return launch_auto<T, 192, 128, 2, 4>(p, stream);
-    case 60: return launch_auto<T, 128, 256, 4, 4>(p, stream);
-    case 63: return launch_auto<T, 64, 128, 2, 4>(p, stream);
-    case 70: return launch_auto<T, 256, 160, 8, 2>(p, stream);   // 80/160-wide tiles: yolov5x / yolov5m channel counts
-    case 71: return launch_auto<T, 256, 160, 4, 2>(p, stream);
-    case 72: return launch_auto<T, 128, 160, 4, 2>(p, stream);
-    case 73: return launch_auto<T, 256, 80, 4, 1>(p, stream);
-    case 74: return launch_auto<T, 256, 80, 8, 1>(p, stream);
-    case 75: return launch_auto<T, 128, 80, 4, 1>(p, stream);
-#ifdef CFT_PROBES   // timing probes / A-B variants (tools/build_probes.sh): results of 1xx/2xx/3xx/16xx are wrong by construction
-    case 3223: return launch_conv<T, 128, 128, 2, 4, true, 32>(p, stream);   // 32xx: bias loaded at the epilogue (round-1 placement)
-    case 3251: return launch_conv<T, 192, 128, 2, 4, true, 32>(p, stream);
-    case 3227: return launch_conv<T, 256, 256, 4, 4, true, 32>(p, stream);
-    case 6427: return launch_conv<T, 256, 256, 4, 4, true, 64>(p, stream);   // 64xx: tap-major K walk for every layer (round-2 A/B)
-    case 1627: return launch_conv<T, 256, 256, 4, 4, true, 16>(p, stream);
-    case 127: return launch_conv<T, 256, 256, 4, 4, true, 1>(p, stream);
-    case 227: return launch_conv<T, 256, 256, 4, 4, true, 2>(p, stream);
-    case 327: return launch_conv<T, 256, 256, 4, 4, true, 3>(p, stream);
-    case 91: if (ring_ok<T>(p)) return launch_ring<T>(p, stream); return launch_auto<T, 256, 256, 4, 4>(p, stream);   // the 8-wave kernel wherever eligible
-    case 190: if (ring_ok<T>(p)) return launch_ring<T, 1>(p, stream); break;    // ring kernel: no global loads after the prologue's
-    case 290: if (ring_ok<T>(p)) return launch_ring<T, 2>(p, stream); break;    // no MFMAs
-    case 1690: if (ring_ok<T>(p)) return launch_ring<T, 16>(p, stream); break;  // no epilogue
-#endif
+    case CFT_CONV_REGISTER_STAGED: return launch_conv<T, 128, 128, 2, 2, false>(p, stream);   // register-staged baseline
+#define X(id, BM, BN, WGM, WGN) case id: return launch_auto<T, BM, BN, WGM, WGN>(p, stream);
+    CONV_TILE_VARIANTS(X)
+#undef X
     default: break;
   }
   // Automatic choice (measured on MI355X with tools/gemm_bench.py, yolov5l+CFTx3 layer shapes, bf16):
@@ -599,18 +570,13 @@ static int dispatch_conv(const ConvParams& p, hipStream_t stream) {
   const bool wide_ok = pad256 * 100 <= pad128 * 115;
   // the hand-scheduled 8-wave kernel (conv_gemm_asm.hip: bit-identical, K loop at 1.27 instead of 1.5 us per 256-row step) from 12 K steps on (below that
   // the 16-wave kernel's shorter prologue + epilogue outweigh the loop, profiles/r06_asm_kloop.md), its tile height picked so that the tile count
-  // fills whole rounds of the CUs; variant 97: the round-5 choice
+  // fills whole rounds of the CUs; CFT_CONV_ROUND5: the choice without it
   static const int asm_min_steps = [] { const char* e = getenv("CFT_ASM_MIN_STEPS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 12; }();   // (tuning knob)
-  if (wide_ok && g_conv_variant != 97 && p.Kpad >= asm_min_steps * 64 && p.ksplit <= 1 && conv_asm_ok(p, dtype_code<T>())) {
+  if (wide_ok && g_conv_variant != CFT_CONV_ROUND5 && p.Kpad >= asm_min_steps * 64 && p.ksplit <= 1 && conv_asm_ok(p, dtype_code<T>())) {
     const int tile = conv_asm_choose(p);
     if (tile >= 0) return conv_asm_launch(p, dtype_code<T>(), tile, stream);
   }
-  if (wide_ok && p.Kpad >= 256 && tiles(256, 256) >= kCUs) {
-#ifdef CFT_PROBES
-    if (g_conv_variant == 90 && ring_ok<T>(p)) return launch_ring<T>(p, stream);    // A/B: the 8-wave kernel in place of the 16-wave 256x256 tile
-#endif
-    return launch_auto<T, 256, 256, 4, 4>(p, stream);
-  }
+  if (wide_ok && p.Kpad >= 256 && tiles(256, 256) >= kCUs) return launch_auto<T, 256, 256, 4, 4>(p, stream);
   if (wide_ok && tiles(128, 256) >= kCUs) return launch_auto<T, 128, 256, 4, 4>(p, stream);   // e.g. CFT fc2 at M = 8192
   if (tiles(192, 128) >= 2 * kCUs) return launch_auto<T, 192, 128, 2, 4>(p, stream);
   if (tiles(128, 128) >= 2 * kCUs) return launch_auto<T, 128, 128, 2, 4>(p, stream);
@@ -679,11 +645,11 @@ static bool chain_ok(const ConvParams& p, int n2, int dtype) {
 template <typename T>
 static int dispatch_chain(const ConvParams& p, hipStream_t stream) {
   if constexpr (sizeof(T) == 2) {
-    if (p.N == 128) return launch_conv<T, 192, 128, 2, 4, true, 0, true, true>(p, stream);   // two workgroups per CU (80 KiB)
-    // 256-channel first layer: the 8-wave kernel with the hand-scheduled first K loop (conv_gemm_asm.hip; variant 97: the 16-wave chained kernel)
-    if (g_conv_variant != 97 && conv_asm_chain_ok(p, dtype_code<T>())) return conv_asm_chain_launch(p, dtype_code<T>(), stream);
-    if (p.y1 != nullptr) return launch_conv<T, 256, 256, 4, 4, true, 0, true, true, true>(p, stream);   // + shortcut (cft_conv2d_chain_res)
-    return launch_conv<T, 256, 256, 4, 4, true, 0, true, true>(p, stream);                   // 16 waves, all 160 KiB
+    if (p.N == 128) return launch_conv<T, 192, 128, 2, 4, true, true, true>(p, stream);   // two workgroups per CU (80 KiB)
+    // 256-channel first layer: the 8-wave kernel with the hand-scheduled first K loop (conv_gemm_asm.hip; CFT_CONV_ROUND5: the 16-wave chained kernel)
+    if (g_conv_variant != CFT_CONV_ROUND5 && conv_asm_chain_ok(p, dtype_code<T>())) return conv_asm_chain_launch(p, dtype_code<T>(), stream);
+    if (p.y1 != nullptr) return launch_conv<T, 256, 256, 4, 4, true, true, true, true>(p, stream);   // + shortcut (cft_conv2d_chain_res)
+    return launch_conv<T, 256, 256, 4, 4, true, true, true>(p, stream);                   // 16 waves, all 160 KiB
   } else return CFT_EINVAL;
 }
 
@@ -745,7 +711,7 @@ extern "C" int cft_linear_splitk(const void* x, const void* w, const float* bias
   CFT_REQUIRE((long)splits * rows * n < (1L << 31), "cft_linear_splitk: partial-sum buffer exceeds 2^31 elements");
   p.ksplit = splits; p.ksteps = kpad / bk / splits;
   const int saved = g_conv_variant;
-  if (saved == 900 || saved == 1) g_conv_variant = 0;   // (variants 900 / 1 force the generic address path: split-K lives on the uniform walk)
+  if (saved == CFT_CONV_GENERIC_WALK || saved == CFT_CONV_REGISTER_STAGED) g_conv_variant = CFT_CONV_AUTO;   // (both force the generic address path: split-K lives on the uniform walk)
   int st = CFT_EINVAL;
   CFT_DISPATCH_DTYPE(dtype, T, st = dispatch_conv<T>(p, as_stream(stream)));
   g_conv_variant = saved;

@@ -790,46 +790,6 @@ def test_asm_gemm_kernel_linear_forms(dev, dtype, rows, K, N):
         assert torch.equal(c, outs[96][2])
 
 
-@pytest.mark.parametrize("dtype", LOWP, ids=["bf16", "f16"])
-def test_probe_build_8wave_kernel_is_bit_identical(dev, dtype):
-    """The 8-wave register-double-buffered 256x256 kernel (csrc/probes/conv_ring.hip, probe build only: it is slower than the shipped 16-wave
-    kernel, profiles/r04_gemm_experiments.md) against the generic path of the same library, bit for bit, on the eligible cases above
-    plus a wide layer with two N tiles.  Skipped when libcft_hip_probes.so has not been built (tools/build_probes.sh)."""
-    import os
-    from msod_amd import _lib, ops
-    probes = os.path.join(os.path.dirname(_lib.LIB_PATH), "libcft_hip_probes.so")
-    if not os.path.exists(probes):
-        pytest.skip("probe build absent")
-    saved = (_lib._lib, _lib.LIB_PATH)
-    _lib._lib, _lib.LIB_PATH = None, probes
-    try:
-        try:
-            lib = _lib.load()
-            stale = lib.cft_abi_version() != _lib.ABI_VERSION
-        except AttributeError:          # built from older sources: an export is missing
-            stale = True
-        if stale:
-            pytest.skip("probe build is older than the product library (re-run tools/build_probes.sh)")
-        for case in [c for c in STAGGERED_CASES if c[3] % 64 == 0] + [(2, 24, 24, 256, 512, 3, 1, True), (1, 40, 40, 512, 256, 1, 1, False)]:
-            B, H, W, Cin, Cout, k, s_, use_res = case
-            x = _q(_rnd(B, Cin, H, W, seed=91), dtype)
-            w = _q(_rnd(Cout, Cin, k, k, seed=92, scale=1.0 / math.sqrt(Cin * k * k)), dtype)
-            pk = ops.pack_conv(w, _rnd(Cout, seed=93, scale=0.5), dtype, s=s_, device=dev)
-            xd = to_dev_nhwc(x, dev, dtype)
-            outs = {}
-            for v in (900, 91):
-                lib.cft_set_conv_variant(v)
-                try:
-                    y0 = ops.conv2d(xd, pk, 1)
-                    outs[v] = ops.conv2d(xd, pk, 1, residual=y0.clone() if use_res else None)
-                    torch.cuda.synchronize()
-                finally:
-                    lib.cft_set_conv_variant(0)
-            assert torch.equal(outs[900], outs[91]), case
-    finally:
-        _lib._lib, _lib.LIB_PATH = saved
-
-
 def test_clock_probe_reports_ticks_and_work(dev):
     """cft_clock_probe (bench.py's shader-clock reading): spins for the requested wall-clock time and reports shader-clock
     ticks, wall-clock ticks and the dependent FMAs executed; the shader clock it implies is a plausible GPU clock."""

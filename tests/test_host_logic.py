@@ -182,6 +182,44 @@ def test_header_parser_on_literal_snippets():
             _lib.parse_header(bad)
 
 
+def test_conv_variant_setter_knows_its_ids():
+    """cft_set_conv_variant takes the ids of csrc/conv_gemm.hip's table (the forced tiles of test_gpu_ops.TILE_VARIANTS and the named
+    CFT_CONV_* ids of the header) and no other: an unknown id returns -1, names itself in cft_last_error and leaves the setting as it
+    was.  The setting is per host thread.  Nothing is launched: no GPU needed."""
+    import threading
+    from test_gpu_ops import TILE_VARIANTS
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libcft_hip.so is not built")
+    lib = _lib.load()
+    named = [_lib._consts[k] for k in ("CFT_CONV_AUTO", "CFT_CONV_REGISTER_STAGED", "CFT_CONV_ASM", "CFT_CONV_ROUND5", "CFT_CONV_GENERIC_WALK")]
+    assert named == [0, 1, 96, 97, 900] and _lib._consts["CFT_CONV_ASM_TILE"] == 960
+    known = sorted(set(TILE_VARIANTS) | set(named) | {_lib._consts["CFT_CONV_ASM_TILE"] + t for t in (1, 2, 3, 4)})
+    assert lib.cft_set_conv_variant(0) >= 0
+    try:
+        prev = 0
+        for v in known:                                   # every known id round-trips: the next call returns it as the previous value
+            assert lib.cft_set_conv_variant(v) == prev, v
+            prev = v
+        assert lib.cft_set_conv_variant(27) == prev
+        for bad in (5, 91, 9201):
+            assert lib.cft_set_conv_variant(bad) == -1
+            assert str(bad).encode() in lib.cft_last_error()
+            assert lib.cft_set_conv_variant(27) == 27     # the previous value stayed in force
+        seen = []
+
+        def other():
+            seen.append(lib.cft_set_conv_variant(51))     # a fresh thread starts at the automatic choice
+            seen.append(lib.cft_set_conv_variant(0))
+
+        t = threading.Thread(target=other)
+        t.start()
+        t.join()
+        assert seen == [0, 51]
+        assert lib.cft_set_conv_variant(0) == 27          # ... and its 51 never showed here
+    finally:
+        lib.cft_set_conv_variant(0)
+
+
 class _OnGpu(torch.Tensor):
     """A meta tensor that says it lives on the GPU: the tensor forms of the eligibility predicates refuse anything else, and they only
     read its shape, strides and dtype."""

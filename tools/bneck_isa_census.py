@@ -183,7 +183,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--source", default=SOURCE)
     ap.add_argument("--kernels", default="bottleneck128c_kernel,bottleneck64r_kernel", help="substrings of the demangled kernel names")
-    ap.add_argument("--define", action="append", default=[], help="extra -D flags, e.g. CFT_PROBES")
+    ap.add_argument("--define", action="append", default=[], help="extra -D flags")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     res = census(compile_asm(a.source, ["-D" + d for d in a.define]), a.source)

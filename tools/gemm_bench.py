@@ -1,7 +1,8 @@
 """Micro-benchmark of cft_conv2d tile variants on the layer shapes that dominate
 yolov5l+CFTx3 @ 640x640, batch 64 (run on the GPU box; writes gpurun_out/gemm_bench.json).
 
-    python tools/gemm_bench.py [--variants 0,1,2,5] [--iters 20]
+    python tools/gemm_bench.py [--variants 0,27,51] [--iters 20]
+The variants are ids of cft_set_conv_variant (include/cft_hip.h); an id the library does not know ends the run.
 """
 import argparse
 import json
@@ -60,7 +61,7 @@ SHAPES = [
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="1,2,5,9")
+    ap.add_argument("--variants", default="0,27,51")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3, help="timed passes per variant, interleaved over the variants (A B C A B C ...): the median is reported")
     ap.add_argument("--warm", type=int, default=10, help="untimed launches before every timed pass (a pass that follows idle time runs at boost clocks: "
@@ -69,13 +70,18 @@ def main():
     ap.add_argument("--used", action="store_true", help="only the shapes that occur in the cfg3 forward (count > 0)")
     ap.add_argument("--out", default="gemm_bench.json")
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--lib", default="", help="load this library instead of the product one (tools/build_probes.sh: libcft_hip_probes.so with the timing probes)")
     args = ap.parse_args()
     variants = [int(v) for v in args.variants.split(",")]
     dev = torch.device("cuda:0")
-    if args.lib:
-        _lib.LIB_PATH = os.path.abspath(args.lib)
     lib = _lib.load()
+
+    def set_variant(v):
+        if lib.cft_set_conv_variant(v) == -1:
+            sys.exit(f"gemm_bench: {lib.cft_last_error().decode(errors='replace')}")
+
+    for v in variants:                           # an unknown id ends the run here, before anything is timed
+        set_variant(v)
+    set_variant(0)
     dtype = {"bf16": torch.bfloat16, "f16": torch.float16}[args.dtype]
     results = []
     g = torch.Generator().manual_seed(0)
@@ -99,7 +105,7 @@ def main():
         ref = None
         outs, times = {}, {v: [] for v in variants}
         for v in variants:                       # correctness pass (and first-touch) per variant
-            lib.cft_set_conv_variant(v)
+            set_variant(v)
             try:
                 out = ops.conv2d(x, pk, 1, residual=res)
                 torch.cuda.synchronize()
@@ -115,7 +121,7 @@ def main():
             for v in variants:
                 if v not in outs:
                     continue
-                lib.cft_set_conv_variant(v)
+                set_variant(v)
                 out = outs[v][0]
                 for _ in range(args.warm):
                     ops.conv2d(x, pk, 1, residual=res, out=out)
@@ -133,7 +139,7 @@ def main():
                 rec["variants"][v] = {"us": round(us, 1), "tflops": round(flops / us / 1e6, 1), "tbps": round(byts / us / 1e6, 2),
                                       "maxdiff_vs_first": outs[v][1], "passes_us": [round(t, 1) for t in times[v]]}
         del outs
-        lib.cft_set_conv_variant(0)
+        set_variant(0)
         print(json.dumps(rec), flush=True)
         results.append(rec)
         del x, res

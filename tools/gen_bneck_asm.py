@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes multispectral-object-detection_amd/csrc/probes/bottleneck_asm.inc: the hand-scheduled 3x3 loop of bottleneck128a_kernel
-(csrc/probes/bottleneck_asm.hip - probe build only: measured slower than the shipped kernel, profiles/r06_bottleneck128_asm.md) as inline-asm text, one string per (operand type, wave group).
+(csrc/probes/bottleneck_asm.hip at commit 6d0acc9, since removed with the probe build: measured slower than the shipped kernel, profiles/r06_bottleneck128_asm.md) as inline-asm text, one string per (operand type, wave group).
 
 The kernel: one 8-wave workgroup per 16 x 16-pixel tile of a 128-channel Bottleneck; the hidden tensor t = SiLU(W1 x + b1) of the
 tile's 18 x 18 halo patch sits in LDS (two 64-channel planes of 128-byte pixel rows, 16-byte slot s of pixel q = k-granule

@@ -64,9 +64,7 @@ PY
     grep -E "^variant|^best|us " $O/gemm.log | tail -80
     X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
     for v in 97 0 97 0; do timeout 300 python bench.py $X --conv-variant $v > $O/bench_v$v.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/bench_v$v.json'));print('variant $v', d['value'], d['ms_per_step'], d['roofline']['frac'], (d.get('single_in_flight') or {}).get('value'))" | tee -a $O/summary.txt; done ;;
-  bneck)       # the fused Bottleneck kernels against the two launches + ablation probes (probe build)
-    CFT_BENCH_LIB=multispectral-object-detection_amd/libcft_hip_probes.so timeout 600 python tools/bneck_bench.py 128 > $O/bneck128.log 2>&1; echo "bneck128 rc=$?"; cat $O/bneck128.log | tail -12 ;;
-  bneck6)      # round 6: the 16 x 16-tile asm Bottleneck-128 kernel (variant 0) against the round-5 kernel (97): tests, then timing
+  bneck6)      # the fused Bottleneck kernels: tests, then timing of the 128-channel kernel against the two launches it replaces
     timeout 1200 python -m pytest tests/test_gpu_ops.py -q -m gpu -x -k "bottleneck" > $O/tests.log 2>&1; echo "tests rc=$?"; tail -5 $O/tests.log
     timeout 600 python tools/bneck_bench.py 128 > $O/bneck128.log 2>&1; echo "bneck128 rc=$?"; cat $O/bneck128.log | tail -8 ;;
   r6b)         # round 6: whole-forward A/B (variant 97 = round-5 choice, 0 = asm kernels) with the board power sampled during the sustained leg
@@ -85,7 +83,7 @@ PY
       head -40 $O/pmc_3x3_512ch_20x20_variant$v.txt
     done ;;
   pmc6b)       # round 6: counters VERDICT r5 listed as evidence gaps - the shipped bottleneck128c_kernel, and the d = 1024 CFT linears at M = 8 192 (asm kernel, 128-row tiles)
-    bash tools/pmc.sh $O/b128 -- python tools/bneck_bench.py 128 0 > $O/pmc_b128.log 2>&1
+    bash tools/pmc.sh $O/b128 -- python tools/bneck_bench.py 128 --fused-only > $O/pmc_b128.log 2>&1
     python tools/pmc_summary.py $O/b128 bottleneck128c > $O/pmc_bottleneck128c.txt; rm -rf $O/b128; head -40 $O/pmc_bottleneck128c.txt
     for shape in "GPT fc2 4096->1024" "GPT qkv 1024->3072"; do
       tag=$(echo "$shape" | sed -e 's/[^A-Za-z0-9]\+/_/g')
@@ -125,15 +123,6 @@ PY
     run "no conv chain" --no-conv-chain
     run "bs8 default" --batch 8
     run "bs8 no splitk" --batch 8 --no-splitk ;;
-  r5c)         # round 5: the one-kernel stem (Focus + Conv s2 + C3 cv1|cv2): op / model bit-identity tests, A/B on the forward
-    timeout 1500 python -m pytest tests/test_gpu_model.py tests/test_gpu_ops.py -q -m gpu -x -k "stem or chain or focus or depth_first or graph_replay or uint8 or six_channel" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -5 $O/tests.log
-    X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
-    run() { tag=$1; shift; timeout 400 python bench.py $X "$@" > $O/b.json 2>> $O/bench.log; python -c "import json;d=json.load(open('$O/b.json'));r=d['roofline'];print('$tag', d['value'], d['ms_per_step'], (d.get('single_in_flight') or {}).get('value'), r['whole_step']['frac'], r['floors']['algorithmic_gbytes_per_step'], d['config'].get('stream_group_probe_ms_per_step'))" | tee -a $O/summary.txt; }
-    run "stem" --stem; cp gpurun_out/bench_families.json $O/families_stem.json
-    run "default (Focus, then chained Conv + C3)"; cp gpurun_out/bench_families.json $O/families_default.json
-    run "stem" --stem
-    run "default (Focus, then chained Conv + C3)"
-    timeout 300 python tools/stem_bench.py > $O/stem_bench.txt 2>&1; cat $O/stem_bench.txt ;;
   r5d)         # round 5: small-batch regime after the size heuristics (chained 3x3 + shortcut only from 192 tiles; split-K to >= 128 workgroups)
     timeout 600 python -m pytest tests/test_gpu_model.py tests/test_gpu_ops.py -q -m gpu -x -k "chain_res or c3_chain or splitk" > $O/tests.log 2>&1; echo "tests rc=$?" | tee $O/summary.txt; tail -3 $O/tests.log
     X="--full --no-cpu-baseline --no-f16-leg --sustained-steps 0 --no-parity"
