@@ -568,7 +568,8 @@ int cft_detect_decode(const float* logits, int ldl, float* raw, float* pred, con
  * `out_dtype`.  workspace: cft_batchnorm_train_workspace(M, C) bytes of device memory.
  *
  * cft_dropout: in-place nn.Dropout(p) in training mode on a contiguous tensor of n elements (GPT.drop :611, resid_drop
- * :511, the MLP's Dropout :537): element i is kept iff hash(seed, i) >= p * 2^32 and scaled by 1/(1-p).
+ * :511, the MLP's Dropout :537): element i is kept iff hash(seed, i) >= p * 2^32 and scaled by 1/(1-p).  x is 16-byte aligned; n > 0
+ * need not be a multiple of the 16-byte granule: the last n % granule elements are moved byte-exactly, nothing past element n is touched.
  */
 long cft_batchnorm_train_workspace(long M, int C);
 int cft_batchnorm_train(const float* x, int ldx, int xoff, long M, int C,

@@ -175,7 +175,7 @@ extern "C" int cft_batchnorm_train(const float* x, int ldx, int xoff, long M, in
 // Counter-based generator: element i of a call keeps its value iff hash(seed, i) >= p * 2^32 and is scaled by 1/(1-p)
 // (torch.nn.Dropout semantics; torch's own Philox stream cannot be reproduced, parity is statistical - tests/test_train.py).
 template <typename T>
-__global__ void __launch_bounds__(256) dropout_kernel(unsigned char* x, long n_gran, uint32_t thresh, float inv_keep, unsigned long long seed) {
+__global__ void __launch_bounds__(256) dropout_kernel(unsigned char* x, long n_gran, int tail, uint32_t thresh, float inv_keep, unsigned long long seed) {
   constexpr int GE = Elem<T>::GE;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n_gran; idx += (long)gridDim.x * blockDim.x) {
     gran_t* p = reinterpret_cast<gran_t*>(x + idx * 16);
@@ -185,6 +185,20 @@ __global__ void __launch_bounds__(256) dropout_kernel(unsigned char* x, long n_g
     for (int e = 0; e < GE; ++e) v[e] = cft_hash32(seed, (unsigned long long)(idx * GE + e)) >= thresh ? v[e] * inv_keep : 0.0f;
     *p = Elem<T>::pack(v);
   }
+  // the last n % GE elements (fewer than a granule): one thread moves exactly their bytes, so nothing past element n is read or written
+  if (tail > 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    constexpr int ES = 16 / GE;
+    unsigned char* q = x + n_gran * 16;
+    gran_t g = {0u, 0u, 0u, 0u};
+    unsigned char* gb = reinterpret_cast<unsigned char*>(&g);
+    for (int i = 0; i < tail * ES; ++i) gb[i] = q[i];
+    float v[GE];
+    Elem<T>::unpack(g, v);
+#pragma unroll
+    for (int e = 0; e < GE; ++e) v[e] = cft_hash32(seed, (unsigned long long)(n_gran * GE + e)) >= thresh ? v[e] * inv_keep : 0.0f;
+    g = Elem<T>::pack(v);
+    for (int i = 0; i < tail * ES; ++i) q[i] = gb[i];
+  }
 }
 
 extern "C" int cft_dropout(void* x, long n, float p, unsigned long long seed, int dtype, void* stream) {
@@ -192,13 +206,13 @@ extern "C" int cft_dropout(void* x, long n, float p, unsigned long long seed, in
   CFT_REQUIRE(cft_is_dtype(dtype), "cft_dropout: bad dtype");
   CFT_REQUIRE(p >= 0.0f && p < 1.0f, "cft_dropout: p must be in [0, 1)");
   const int ge = cft_granule(dtype);
-  CFT_REQUIRE(n > 0 && n % ge == 0 && ((size_t)x & 15) == 0, "cft_dropout: contiguous, 16-byte aligned tensors with a granule multiple of elements");
+  CFT_REQUIRE(n > 0 && ((size_t)x & 15) == 0, "cft_dropout: contiguous, 16-byte aligned tensors of n > 0 elements");
   if (p == 0.0f) return CFT_OK;
   const uint32_t thresh = (uint32_t)((double)p * 4294967296.0);
   const long n_gran = n / ge;
   long g = (n_gran + 255) / 256;
-  g = g > 4096 ? 4096 : g;
-  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dropout_kernel<T>, dim3((unsigned)g), dim3(256), 0, as_stream(stream), (unsigned char*)x, n_gran, thresh,
-                                                   1.0f / (1.0f - p), seed));
+  g = g > 4096 ? 4096 : (g < 1 ? 1 : g);
+  CFT_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dropout_kernel<T>, dim3((unsigned)g), dim3(256), 0, as_stream(stream), (unsigned char*)x, n_gran, (int)(n % ge),
+                                                   thresh, 1.0f / (1.0f - p), seed));
   return cft_check_launch("dropout_kernel");
 }

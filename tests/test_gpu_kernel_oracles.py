@@ -402,20 +402,22 @@ def test_gpt_upsample_add_dual_per_element(dev, dtype, hw, C):
                        f"upsample_add2 {name} {hw} C{C} {dtype}")
 
 
-def test_detect_decode_per_element(dev):
-    """YOLO decode of fp32 logits (85 outputs per anchor, logits over [-12, 12]) into a slice of the prediction rows: raw is a
-    copy; xy = (2 s - 0.5 + grid) * stride, wh = (2 s)^2 * anchor, the rest s = sigmoid, each within __expf's error carried
-    through the formula plus a few fp32 roundings; rows outside the slice stay zero."""
-    from msod_amd import ops
-    B, ny, nx, na, no, stride, row0 = 2, 20, 24, 3, 85, 16.0, 100
-    logits = _rnd(B, na * no + 1, ny, nx, seed=27, scale=4.0).clamp(-12.0, 12.0)     # ldl = 256: one padding channel
-    anchors = torch.tensor([10., 13., 16., 30., 33., 23.])
-    d = to_dev_nhwc(logits, dev, torch.float32)
-    raw = torch.empty(B, na, ny, nx, no, device=dev)
-    rows = row0 + na * ny * nx + 50
-    pred = torch.zeros(B, rows, no, device=dev)
-    ops.detect_decode(d, raw, pred, anchors.to(dev), na, no, stride, row0)
-    torch.cuda.synchronize()
+DECODE_CASE = dict(B=2, ny=20, nx=24, na=3, no=85, stride=16.0, row0=100, tail=50)
+
+
+def decode_operands():
+    """Seeded operands of the Detect-decode case (shared with tests/test_gpu_memory_hygiene.py): logits [B, ldl, ny, nx] over [-12, 12]
+    with one padding channel, anchors in pixels."""
+    c = DECODE_CASE
+    logits = _rnd(c["B"], c["na"] * c["no"] + 1, c["ny"], c["nx"], seed=27, scale=4.0).clamp(-12.0, 12.0)     # ldl = 256: one padding channel
+    return logits, torch.tensor([10., 13., 16., 30., 33., 23.])
+
+
+def decode_check(logits, anchors, raw, pred, before=None):
+    """raw is a copy; xy = (2 s - 0.5 + grid) * stride, wh = (2 s)^2 * anchor, the rest s = sigmoid, each within __expf's error carried
+    through the formula plus a few fp32 roundings; rows outside the slice keep what they held (``before``; None: zero)."""
+    c = DECODE_CASE
+    B, ny, nx, na, no, stride, row0 = (c[k] for k in ("B", "ny", "nx", "na", "no", "stride", "row0"))
     y = logits[:, :na * no].reshape(B, na, no, ny, nx).permute(0, 1, 3, 4, 2).double()
     assert torch.equal(raw.cpu(), y.float())
     sg = torch.sigmoid(y)
@@ -432,9 +434,29 @@ def test_detect_decode_per_element(dev):
     slope[..., 2:4] = 8 * sg[..., 2:4] * anc
     bound = (slope * dsg + 4 * X.U24 * ref.abs()).numpy()
     got = pred.cpu()
-    X.assert_close(got[:, row0:row0 + na * ny * nx].double().numpy(), ref.reshape(B, -1, no).numpy(), bound.reshape(B, -1, no),
+    n = na * ny * nx
+    X.assert_close(got[:, row0:row0 + n].double().numpy(), ref.reshape(B, -1, no).numpy(), bound.reshape(B, -1, no),
                    torch.float32, None, "detect_decode")
-    assert float(got[:, :row0].abs().max()) == 0.0 and float(got[:, row0 + na * ny * nx:].abs().max()) == 0.0
+    if before is None:
+        assert float(got[:, :row0].abs().max()) == 0.0 and float(got[:, row0 + n:].abs().max()) == 0.0
+    else:
+        assert torch.equal(got[:, :row0], before[:, :row0]) and torch.equal(got[:, row0 + n:], before[:, row0 + n:])
+
+
+def test_detect_decode_per_element(dev):
+    """YOLO decode of fp32 logits (85 outputs per anchor, logits over [-12, 12]) into a slice of the prediction rows: raw is a
+    copy; xy = (2 s - 0.5 + grid) * stride, wh = (2 s)^2 * anchor, the rest s = sigmoid, each within __expf's error carried
+    through the formula plus a few fp32 roundings; rows outside the slice stay zero."""
+    from msod_amd import ops
+    c = DECODE_CASE
+    logits, anchors = decode_operands()
+    d = to_dev_nhwc(logits, dev, torch.float32)
+    raw = torch.empty(c["B"], c["na"], c["ny"], c["nx"], c["no"], device=dev)
+    rows = c["row0"] + c["na"] * c["ny"] * c["nx"] + c["tail"]
+    pred = torch.zeros(c["B"], rows, c["no"], device=dev)
+    ops.detect_decode(d, raw, pred, anchors.to(dev), c["na"], c["no"], c["stride"], c["row0"])
+    torch.cuda.synchronize()
+    decode_check(logits, anchors, raw, pred)
 
 
 # ------------------------------------------------------------------------------ BatchNorm (training mode)
@@ -451,11 +473,10 @@ BN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", BN_CASES, ids=[f"bn{i}" for i in range(len(BN_CASES))])
-def test_batchnorm_train_per_element(dev, case):
-    """cft_batchnorm_train against float64 batch statistics: the output per element, running mean and unbiased running variance
-    (M/(M-1); M = 1 keeps the biased 0).  Channel 0 sits at |mean| = 1e4 sigma; channel 1's row 0 lies 1e3 sigma from its mean."""
-    from msod_amd import ops
+def bn_operands(case):
+    """Seeded operands of one BN_CASES entry (shared with tests/test_gpu_memory_hygiene.py): x [M, pad8(C)] fp32 (channel 0 at |mean| =
+    1e4 sigma; channel 1's row 0 1e3 sigma from its mean), gamma, beta, the running statistics before the call, the shortcut or None
+    and its dtype."""
     M, C, act, rkind, odt, mom = case
     Cp = -(-C // 8) * 8
     gen = torch.Generator().manual_seed(M + C)
@@ -466,29 +487,22 @@ def test_batchnorm_train_per_element(dev, case):
     x[:, 0] = torch.randn(M, generator=gen) * 0.5 + 5000.0
     if C > 1 and M > 1:
         x[0, 1] = mean_c[1] + 1000.0 * sig_c[1]
-    bn = torch.nn.BatchNorm2d(C, momentum=mom).to(dev)
-    with torch.no_grad():
-        bn.weight.copy_(1 + 0.2 * torch.randn(C, generator=gen))
-        bn.bias.copy_(0.2 * torch.randn(C, generator=gen))
-        bn.running_mean.copy_(torch.randn(C, generator=gen))
-        bn.running_var.copy_(torch.rand(C, generator=gen) + 0.5)
-        bn.num_batches_tracked.fill_(3)
-    rm0, rv0 = bn.running_mean.double().cpu(), bn.running_var.double().cpu()
-    gamma, beta = bn.weight.detach().double().cpu(), bn.bias.detach().double().cpu()
-    y32 = x.to(dev).view(M, 1, 1, Cp).permute(0, 3, 1, 2)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=gen), 0.2 * torch.randn(C, generator=gen)
+    rm0, rv0 = torch.randn(C, generator=gen), torch.rand(C, generator=gen) + 0.5
     rdt = odt if rkind == "out" else torch.float32
     res = _q(_rnd(M, C, seed=5), rdt) if rkind else None
-    rd = None
-    if rkind:       # a channel slice of a granule-wide buffer, like the output
-        rbuf = torch.zeros(M, Cp, dtype=rdt, device=dev)
-        rbuf[:, :C] = res.to(dev).to(rdt)
-        rd = rbuf.view(M, 1, 1, Cp).permute(0, 3, 1, 2)[:, :C]
-    out = ops.batchnorm_train(y32, C, bn, act, residual=rd, out_dtype=odt)
-    torch.cuda.synchronize()
+    return dict(x=x, Cp=Cp, gamma=gamma, beta=beta, rm0=rm0, rv0=rv0, res=res, rdt=rdt)
+
+
+def bn_check(case, o, got, rm, rv, m, eps=1e-5):
+    """The output [M, C] per element, running mean and unbiased running variance (momentum ``m``) against float64 batch statistics."""
+    M, C, act, rkind, odt, mom = case
+    x, res = o["x"], o["res"]
+    gamma, beta, rm0, rv0 = o["gamma"].double(), o["beta"].double(), o["rm0"].double(), o["rv0"].double()
     x64 = x[:, :C].double()
     mu = x64.mean(0)
     var = x64.var(0, unbiased=False)
-    sc = gamma / (var + bn.eps).sqrt()
+    sc = gamma / (var + eps).sqrt()
     sh = beta - mu * sc
     v = (x64 * sc + sh).numpy()
     ref = X.act64(v, act) + (res.double().numpy() if rkind else 0.0)
@@ -496,18 +510,43 @@ def test_batchnorm_train_per_element(dev, case):
     # of the statistics (and of sc) moves v - beta = (x - mean) * sc: held to 4e-6 (the parent's single-row pivot: up to 5e-3)
     bound = (X.ulp(ref, odt) + 1.1 * (4 * X.U24 * (np.abs((x64 * sc).numpy()) + np.abs(sh.numpy())) + 4e-6 * np.abs(v - beta.numpy()))
              + X.act_err(v, act) + 4 * X.U24 * np.abs(ref))
-    got = out.permute(0, 2, 3, 1).reshape(M, C).double().cpu().numpy()
+    got = got.double().cpu().numpy()
     # channel 0 (|mean| = 1e4 sigma) loses the last bits to the fp32 affine form, so the rounding-rate floor applies to the others
     X.assert_close(got[:, :1], ref[:, :1], bound[:, :1], odt, None, f"bn {case} ch0")
     X.assert_close(got[:, 1:], ref[:, 1:], bound[:, 1:], odt, FLOOR[odt] if M * C >= 4096 else None, f"bn {case}")
-    m = mom if mom is not None else 1.0 / 4
     unb = var * M / (M - 1) if M > 1 else var
     rm_ref, rv_ref = (1 - m) * rm0 + m * mu, (1 - m) * rv0 + m * unb
-    rm, rv = bn.running_mean.double().cpu(), bn.running_var.double().cpu()
+    rm, rv = rm.double().cpu(), rv.double().cpu()
     var_rel = ((rv - rv_ref).abs() / rv_ref).max().item()
     print(f"[oracle] bn {case}: running_var max rel err {var_rel:.3e}")
     assert ((rm - rm_ref).abs() <= 8 * X.U24 * (rm0.abs() + mu.abs()) + 1e-6 * var.sqrt()).all()
     assert var_rel <= 1e-5, f"running_var relative error {var_rel:.3e}"
+
+
+@pytest.mark.parametrize("case", BN_CASES, ids=[f"bn{i}" for i in range(len(BN_CASES))])
+def test_batchnorm_train_per_element(dev, case):
+    """cft_batchnorm_train against float64 batch statistics: the output per element, running mean and unbiased running variance
+    (M/(M-1); M = 1 keeps the biased 0).  Channel 0 sits at |mean| = 1e4 sigma; channel 1's row 0 lies 1e3 sigma from its mean."""
+    from msod_amd import ops
+    M, C, act, rkind, odt, mom = case
+    o = bn_operands(case)
+    x, Cp, res, rdt = o["x"], o["Cp"], o["res"], o["rdt"]
+    bn = torch.nn.BatchNorm2d(C, momentum=mom).to(dev)
+    with torch.no_grad():
+        bn.weight.copy_(o["gamma"])
+        bn.bias.copy_(o["beta"])
+        bn.running_mean.copy_(o["rm0"])
+        bn.running_var.copy_(o["rv0"])
+        bn.num_batches_tracked.fill_(3)
+    y32 = x.to(dev).view(M, 1, 1, Cp).permute(0, 3, 1, 2)
+    rd = None
+    if rkind:       # a channel slice of a granule-wide buffer, like the output
+        rbuf = torch.zeros(M, Cp, dtype=rdt, device=dev)
+        rbuf[:, :C] = res.to(dev).to(rdt)
+        rd = rbuf.view(M, 1, 1, Cp).permute(0, 3, 1, 2)[:, :C]
+    out = ops.batchnorm_train(y32, C, bn, act, residual=rd, out_dtype=odt)
+    torch.cuda.synchronize()
+    bn_check(case, o, out.permute(0, 2, 3, 1).reshape(M, C), bn.running_mean, bn.running_var, mom if mom is not None else 1.0 / 4, bn.eps)
     assert int(bn.num_batches_tracked) == 4
 
 
