@@ -4,9 +4,14 @@ There is deliberately NO fallback: if the library is missing or the device is no
 op raises.  ``build()`` compiles the library in-tree with hipcc (cross-compiles without a GPU).
 """
 import ctypes
+import functools
+import glob
 import os
 import re
+import shutil
 import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 # torch must be imported BEFORE the library is dlopen'ed: torch ships its own libamdhip64 and a
 # process that first loads the system copy (through libcft_hip.so) and then torch's ends up with
@@ -14,12 +19,12 @@ import subprocess
 import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("CFT_HIP_LIB") or os.path.join(_HERE, "libcft_hip.so")      # (CFT_HIP_LIB: load another build of the library, e.g. one made with tools/build.sh and CFT_OUT)
+BUILT_LIB = os.path.join(_HERE, "libcft_hip.so")                  # what build() writes unless told otherwise
+LIB_PATH = os.environ.get("CFT_HIP_LIB") or BUILT_LIB             # what load() loads (CFT_HIP_LIB: another build of the library, e.g. one made with tools/build.sh and CFT_OUT)
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("runtime.hip", "conv_gemm.hip", "conv_gemm_asm.hip", "focus_conv.hip", "bottleneck.hip", "pointwise.hip", "attention.hip", "attention_tokens.hip", "nms.hip", "train.hip", "metrics.hip", "curves.hip", "confusion.hip", "loss.hip", "autoanchor.hip", "dataset.hip", "detect.hip", "optim.hip", "mosaic.hip", "augment.hip", "jpeg.hip", "jpeg_encode.hip", "tta.hip")
-
 HEADER = os.path.join(_HERE, "..", "include", "cft_hip.h")
-HEADERS = ("cft_common.h", "conv_common.h", "focus_common.h", "bneck_common.h", "metrics_common.h", "resize_common.h", "jpeg_common.h", "conv_gemm_asm.inc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]      # of every compile of the project: the library, the ISA listings of the tests and tools
 
 _SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong}
 _RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
@@ -62,46 +67,95 @@ ACT_NONE, ACT_SILU, ACT_GELU = (_consts[k] for k in ("CFT_ACT_NONE", "CFT_ACT_SI
 _lib = None
 
 
-def missing_symbols():
+def missing_symbols(path=None):
     """The entry points of the header that the built library's bytes do not name (its dynamic string table holds every export): a
     library from before an entry point was added is stale whatever its timestamp says.  Nothing is loaded."""
-    with open(LIB_PATH, "rb") as fh:
+    with open(path or LIB_PATH, "rb") as fh:
         blob = fh.read()
     return [name for name in SIGNATURES if name.encode() + b"\0" not in blob]
 
 
-def build(verbose=False):
-    """Compile every HIP source for gfx950 into ``libcft_hip.so`` next to this file."""
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [HEADER]
-    newest = max(os.path.getmtime(p) for p in srcs + hdrs)
-    if os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest and not missing_symbols():
-        return LIB_PATH
-    # one object per source, compiled concurrently (only the stale ones), then one link
-    hdr_time = max(os.path.getmtime(h) for h in hdrs)
-    obj_dir = os.path.join(_HERE, "build")
+def sources():
+    """Every HIP source of the library: a file dropped into csrc/ is built."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+
+
+def staleness_inputs():
+    """What every object depends on besides its own source: a file dropped into csrc/ rebuilds."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [HEADER]
+
+
+SOURCES = tuple(os.path.basename(p) for p in sources())      # the names, for readers that ask "is x.hip built"; no list is kept by hand
+
+
+def _compile(cmd):
+    status = subprocess.Popen(cmd).wait()
+    if status != 0:
+        raise subprocess.CalledProcessError(status, cmd)
+
+
+def build(verbose=False, out=None, extra_flags=()):
+    """Compile every HIP source for gfx950 into ``libcft_hip.so`` next to this file (wherever CFT_HIP_LIB points: that is load()'s
+    business), or into ``out``.  Another ``out`` or ``extra_flags`` compile everything afresh in an object directory of their own."""
+    global _lib
+    srcs, deps = sources(), staleness_inputs()
+    in_tree = out is None and not extra_flags
+    out = BUILT_LIB if out is None else os.path.abspath(out)
+    newest = max(os.path.getmtime(p) for p in srcs + deps)
+    if in_tree and os.path.exists(out) and os.path.getmtime(out) >= newest and not missing_symbols(out):
+        return out
+    # one object per source (in the tree's own cache only the stale ones), a bounded number of compiles at a time, then one link
+    dep_time = max(os.path.getmtime(h) for h in deps)
+    obj_dir = os.path.join(_HERE, "build") if in_tree else tempfile.mkdtemp(prefix="cft_build_")
     os.makedirs(obj_dir, exist_ok=True)
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
-    jobs, objs = [], []
+    cmds, objs = [], []
     for src in srcs:
         obj = os.path.join(obj_dir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
-        if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_time):
-            continue
-        cmd = ["hipcc"] + flags + ["-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd))
-        jobs.append((cmd, subprocess.Popen(cmd)))
-    for cmd, p in jobs:
-        if p.wait() != 0:
-            raise subprocess.CalledProcessError(p.returncode, cmd)
-    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
+        if not (os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), dep_time)):
+            cmds.append([HIPCC] + HIPCC_FLAGS + list(extra_flags) + ["-c", src, "-o", obj])
+    cmds.append([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + list(extra_flags))
     if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    global _lib
-    _lib = None
-    return LIB_PATH
+        print("\n".join(" ".join(cmd) for cmd in cmds))
+    pool = ThreadPoolExecutor(max(1, min(16, int(os.environ.get("MAX_JOBS", 16)))))
+    try:
+        list(pool.map(_compile, cmds[:-1]))
+        _compile(cmds[-1])
+    finally:
+        pool.shutdown(cancel_futures=True)
+        if not in_tree:
+            shutil.rmtree(obj_dir, ignore_errors=True)
+    if in_tree:
+        _lib = None          # load() opens the new library
+    return out
+
+
+def device_asm(src, extra=()):
+    """The gfx950 assembly hipcc makes of a HIP source's device code, with the flags of the build (+ ``extra``); a source is
+    compiled once per process.  FileNotFoundError without hipcc."""
+    return _device_asm(os.path.abspath(src), tuple(extra))
+
+
+@functools.lru_cache(maxsize=None)
+def _device_asm(src, extra):
+    cmd = [HIPCC] + HIPCC_FLAGS + ["-S", "--cuda-device-only", *extra, "-o", "-", src]
+    return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+
+
+def kernel_notes(asm):
+    """{kernel name: {key: int}} of every integer key of the entries under ``amdhsa.kernels:`` in a listing.  An entry opens at
+    ``  - .key:`` whichever key comes first, with a value on the line or not (``.args:``); its own keys sit four columns in, those of
+    its arguments deeper."""
+    entries = []
+    for line in asm[asm.index("amdhsa.kernels:"):].split("\n")[1:]:
+        if not line.startswith("  "):
+            break
+        m = re.match(r"(  - |    )\.(\w+):\s*(.*?)\s*$", line)
+        if m and m.group(1) == "  - ":
+            entries.append({})
+        if m:
+            entries[-1][m.group(2)] = m.group(3)
+    return {e["name"]: {k: int(v) for k, v in e.items() if v.isdigit()} for e in entries}
 
 
 def load():

@@ -1,5 +1,22 @@
-"""Shared helpers of the parity tests: tensor layout conversion and error metrics."""
+"""Shared helpers of the tests: tensor layout conversion, error metrics, the compiler's listing of a HIP source."""
+import pytest
 import torch
+
+
+def device_asm(src, extra=()):
+    """_lib.device_asm, or a skip where there is no hipcc."""
+    import msod_amd  # noqa: F401
+    from msod_amd import _lib
+    try:
+        return _lib.device_asm(src, extra)
+    except FileNotFoundError:
+        pytest.skip("hipcc not available")
+
+
+def kernel_notes(src):
+    """{kernel name: {note key: int}} of every kernel hipcc makes of a HIP source."""
+    from msod_amd import _lib
+    return _lib.kernel_notes(device_asm(src))
 
 
 def to_dev_nhwc(x, dev, dtype):

@@ -1,9 +1,6 @@
 """Host tests of the confusion matrix and the save_txt / save_json formats: tests/confusion_ref.py (a restatement from the rules)
 and the package's formatters against the reference's own results in tests/golden/eval/confusion_cases.pt."""
 import os
-import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -11,6 +8,7 @@ import pytest
 import torch
 
 import confusion_ref
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "eval", "confusion_cases.pt")
@@ -116,20 +114,11 @@ def test_header_declares_new_exports_returning_int():
     assert len(_lib.SIGNATURES["cft_eval_confusion"][1]) == 19
 
 
-def test_confusion_kernels_use_no_scratch(tmp_path):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "multispectral-object-detection_amd", "csrc", "confusion.hip")
-    out = tmp_path / "confusion.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", src, "-o", str(out)],
-                   check=True, capture_output=True)
-    text = out.read_text()
-    meta = text[text.index("amdhsa.kernels:"):]
-    entries = re.split(r"\n  - (?=\.)", meta)[1:]
-    names = [re.search(r"\n    \.name:\s+(\S+)", "\n    " + e).group(1) for e in entries]
-    assert len(entries) == 2 and any("eval_confusion_kernel" in n for n in names) and any("eval_export_kernel" in n for n in names), names
-    for name, m in zip(names, entries):
-        assert re.search(r"\.private_segment_fixed_size:\s+0\n", m), name
-        assert re.search(r"\.vgpr_spill_count:\s+0\n", m), name
-        assert re.search(r"\.sgpr_spill_count:\s+0\n", m), name
+def test_confusion_kernels_use_no_scratch():
+    notes = helpers.kernel_notes(os.path.join(ROOT, "multispectral-object-detection_amd", "csrc", "confusion.hip"))
+    names = sorted(notes)
+    assert len(notes) == 2 and any("eval_confusion_kernel" in n for n in names) and any("eval_export_kernel" in n for n in names), names
+    for name, m in notes.items():
+        assert m["private_segment_fixed_size"] == 0, name
+        assert m["vgpr_spill_count"] == 0, name
+        assert m["sgpr_spill_count"] == 0, name

@@ -5,8 +5,6 @@ of the asm GEMM's accumulator registers in the compiler's output."""
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import exact_ref as X
+import helpers
 from helpers import rel_err, tol
 
 FLOOR = {torch.bfloat16: 0.99, torch.float16: 0.95}      # host-side floors (the device floors live in test_gpu_kernel_oracles.py)
@@ -208,14 +207,8 @@ def test_agpr_scan_flags_a_write_outside_an_asm_block():
 
 
 @pytest.fixture(scope="module")
-def asm_listing(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "conv_gemm_asm.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", ASM_SRC, "-o", str(out)],
-                   check=True, capture_output=True)
-    return out.read_text()
+def asm_listing():
+    return helpers.device_asm(ASM_SRC)
 
 
 def _expected_kernel_count():
@@ -233,14 +226,14 @@ def test_asm_gemm_accumulators_stay_in_asm_blocks(asm_listing):
     """The asm GEMM keeps its accumulators a0-a127 live across separate inline-asm statements, a dependency the compiler cannot see:
     if it ever allocated an AGPR itself, or spilled, a tile would come out wrong on the GPU.  Check it in the compiler's output: no
     scratch, no spills, no AGPR operand outside an inline-asm block, and every instantiated kernel present."""
-    meta = asm_listing[asm_listing.index("amdhsa.kernels:"):]
-    entries = [e for e in re.split(r"\n  - (?=\.)", meta)[1:]]
-    kernels = [(re.search(r"\n    \.name:\s+(\S+)", "\n    " + e).group(1), e) for e in entries]
-    assert len(kernels) == _expected_kernel_count(), [n for n, _ in kernels]
-    for name, m in kernels:
-        assert re.search(r"\.private_segment_fixed_size:\s+0\n", m), name
-        assert re.search(r"\.vgpr_spill_count:\s+0\n", m), name
-        assert re.search(r"\.sgpr_spill_count:\s+0\n", m), name
+    import msod_amd  # noqa: F401
+    from msod_amd import _lib
+    kernels = _lib.kernel_notes(asm_listing)
+    assert len(kernels) == _expected_kernel_count(), sorted(kernels)
+    for name, m in kernels.items():
+        assert m["private_segment_fixed_size"] == 0, name
+        assert m["vgpr_spill_count"] == 0, name
+        assert m["sgpr_spill_count"] == 0, name
     outside, inside = agprs_outside_asm_blocks(asm_listing)
     assert outside == [], outside[:10]
     assert inside > 1000
@@ -248,9 +241,8 @@ def test_asm_gemm_accumulators_stay_in_asm_blocks(asm_listing):
     # register file and the AGPRs start at accum_offset, so an under-sized AGPR block would alias the accumulators with other registers.
     hi = max([int(up) for up in re.findall(r"\ba\[\d+:(\d+)\]", asm_listing)] + [int(n) for n in re.findall(r"\ba(\d+)\b", asm_listing)])
     assert hi == 127, hi
-    for name, m in kernels:
-        agprs = re.search(r"\.agpr_count:\s+(\d+)", m)
-        assert agprs and int(agprs.group(1)) >= hi + 1, (name, agprs and agprs.group(1))
+    for name, m in kernels.items():
+        assert m["agpr_count"] >= hi + 1, (name, m["agpr_count"])
     blocks = re.findall(r"\.amdhsa_next_free_vgpr (\d+)\s*\n(?:.*\n){0,3}?\s*\.amdhsa_accum_offset (\d+)", asm_listing)
     assert len(blocks) == len(kernels)
     for nfv, acc in blocks:

@@ -1,6 +1,6 @@
 """Instruction census of the fused Bottleneck kernels (csrc/bottleneck.hip), from the compiler's gfx950 assembly.  No GPU needed.
     python tools/bneck_isa_census.py [--source FILE.hip] [--kernels SUBSTR[,SUBSTR]] [--json]
-The source is compiled with `hipcc --offload-arch=gfx950 -O3 -S --cuda-device-only -gline-tables-only`; every instruction is given
+The source is compiled with the flags of the build (`_lib.device_asm`) and `-gline-tables-only`; every instruction is given
 the phase of the last `.loc` line that points into the source file itself (inlined helpers of the headers take the phase of their
 outermost call site).  Phases are opened in the source by comments of the form `// [census: NAME]` or `// [census: NAME xN]` (N = how often the
 phase runs per tile, e.g. a rolled tap loop) and last to the next marker or to the end of the kernel; N weighs only the instructions
@@ -15,9 +15,11 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import msod_amd  # noqa: E402, F401
+from msod_amd import _lib  # noqa: E402
 SOURCE = os.path.join(ROOT, "multispectral-object-detection_amd", "csrc", "bottleneck.hip")
 CLASSES = ("MFMA", "TRANS", "VALU", "SALU", "SYNC", "LDS", "VMEM", "SMEM")
 _TRANS = ("v_exp", "v_rcp", "v_log", "v_rsq", "v_sqrt", "v_sin", "v_cos")
@@ -45,13 +47,8 @@ def classify(mnemonic):
 
 
 def compile_asm(source, extra=()):
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "bneck.s")
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-gline-tables-only",
-               "-I", os.path.dirname(SOURCE), *extra, "-o", out, source]
-        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        with open(out) as fh:
-            return fh.read()
+    """The listing with line tables: the project's one compile recipe (_lib.device_asm) plus -gline-tables-only."""
+    return _lib.device_asm(source, ("-gline-tables-only", "-I", os.path.dirname(SOURCE), *extra))
 
 
 def source_phases(source):
@@ -72,19 +69,6 @@ def phase_of(marks, line):
             break
         cur = (name, rep)
     return cur
-
-
-def metadata(asm):
-    """name -> {vgpr_count, sgpr_spill_count, vgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size} from the
-    amdhsa.kernels notes."""
-    meta = {}
-    for block in re.split(r"\n\s+- \.agpr_count:", asm)[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if not name:
-            continue
-        meta[name.group(1)] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                               for k in ("vgpr_count", "sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
-    return meta
 
 
 def census(asm, source):
@@ -146,7 +130,7 @@ def census(asm, source):
                 kernel["order"].append(phase)
                 kernel["counts"][phase] = dict.fromkeys(CLASSES, 0)
             kernel["counts"][phase][cls] += 1
-    meta = metadata(asm)
+    meta = _lib.kernel_notes(asm)
     out = {}
     for name, k in result.items():
         order = sorted(k["order"], key=lambda ph: (next((i for i, mk in enumerate(marks) if mk[1] == ph[0]), -1), ph[1]))
