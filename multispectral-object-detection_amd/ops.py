@@ -33,8 +33,12 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _is_cuda(t):
+    return t.is_cuda
+
+
 def _require_cuda(t, what):
-    if not t.is_cuda:
+    if not _is_cuda(t):
         raise RuntimeError(f"{what}: tensor is on {t.device}; this package runs on MI355X only "
                            "(no CPU fallback - use oracle/ for a CPU reference)")
 
@@ -52,10 +56,15 @@ def to_nhwc(x, dtype=None, cpad=None):
     """Any strided [B,C,H,W] fp32/bf16/half tensor -> fresh NHWC buffer in ``dtype`` with the channel count
     padded to ``cpad`` (default: next granule multiple; padding channels zero) - the cft_to_nhwc kernel."""
     _require_cuda(x, "to_nhwc")
+    if x.dim() != 4:
+        raise ValueError(f"to_nhwc: expected a [B,C,H,W] tensor, got {tuple(x.shape)}")
     B, C, H, W = x.shape
     dtype = dtype or x.dtype
+    _dt(x.dtype), _dt(dtype)
     ge = granule(dtype)
     cp = cpad or ((C + ge - 1) // ge) * ge
+    if cp < C or cp % ge:
+        raise ValueError(f"to_nhwc: cpad {cp} must be a multiple of the {ge}-element granule >= {C} channels")
     y = new_nhwc(B, H, W, cp, dtype, x.device)
     st = _lib.load().cft_to_nhwc(x.data_ptr(), _dt(x.dtype), x.stride(0), x.stride(1), x.stride(2), x.stride(3),
                                  y.data_ptr(), cp, 0, B, C, cp, H, W, _dt(dtype), _stream())
@@ -71,7 +80,7 @@ def as_nhwc(x):
     ld = x.stride(3)
     ok = x.stride(1) == 1 and ld >= C and x.stride(2) == W * ld and x.stride(0) == H * W * ld
     ge = granule(x.dtype)
-    ok = ok and ld % ge == 0 and (x.storage_offset() % ge == 0)
+    ok = ok and ld % ge == 0 and x.storage_offset() % ge == 0 and x.data_ptr() % 16 == 0
     if not ok:
         if C % ge:
             raise ValueError(f"as_nhwc: {C} channels is not a multiple of the {ge}-element granule")
@@ -86,6 +95,90 @@ def _view_ld(x, what):
     if not (x.stride(1) == 1 and ld >= C and x.stride(2) == W * ld and x.stride(0) == H * W * ld):
         raise ValueError(f"{what}: tensor is not an NHWC buffer or a channel slice of one")
     return ld
+
+
+# ------------------------------------------------------------------------------ argument guards
+# Metadata only (shape, stride, dtype, device, data_ptr() % 16): nothing here synchronises, allocates or reads device memory.
+# RuntimeError: wrong device; TypeError: wrong dtype; ValueError: shape, stride, alignment or overlap.
+def _on(t, ref, what):
+    if t.device != ref.device:
+        raise RuntimeError(f"{what}: tensor is on {t.device}, expected {ref.device}")
+
+
+def _is(t, dtype, what):
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: dtype {t.dtype}, expected {dtype}")
+
+
+def _packed_for(pk, x, what, dtype=None):
+    """The packed weights are in the dtype the kernel computes in (the dtype of ``x``) and on the device of ``x``."""
+    _on(pk.w, x, f"{what} packed weight")
+    _is(pk.w, dtype or x.dtype, f"{what} packed weight")
+
+
+def _out_view(t, ref, what, shape=None, ge=None):
+    """ld of an NHWC view the kernel writes, adds or updates in place (never copied): on the device of ``ref``, a compute dtype, the
+    shape asked for, ld a multiple of the granule (``ge``: 8 for what cft_conv2d and its relatives store, whatever the dtype) and the
+    base pointer 16-byte aligned (the kernels store whole granules)."""
+    _on(t, ref, what)
+    _dt(t.dtype)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    ld = _view_ld(t, what)
+    ge = ge or granule(t.dtype)
+    if ld % ge or t.data_ptr() % 16:
+        raise ValueError(f"{what}: channels per pixel ({ld}) must be a multiple of {ge} and the base pointer 16-byte aligned (a channel "
+                         f"slice starts at a granule multiple)")
+    return ld
+
+
+def _rows_ld(t, ref, what, shape=None, ge=None):
+    """Row stride of a [rows, C] operand (``linear`` x / out / residual, ``add_rows_``): unit column stride, a row stride that is a granule
+    multiple >= C, a 16-byte aligned base."""
+    _on(t, ref, what)
+    _dt(t.dtype)
+    if t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected {tuple(shape) if shape is not None else '[rows, C]'}")
+    ld = t.stride(0)
+    ge = ge or granule(t.dtype)
+    if t.stride(1) != 1 or ld < t.shape[1] or ld % ge or t.data_ptr() % 16:
+        raise ValueError(f"{what}: needs unit column stride, a row stride (a multiple of {ge}) >= {t.shape[1]} and a 16-byte aligned base, "
+                         f"got strides {tuple(t.stride())}")
+    return ld
+
+
+def _vec(t, ref, shape, what, dtype=torch.float32):
+    """An auxiliary tensor the kernel reads through a raw pointer (gamma, beta, pos_emb, anchors, BN parameters): dense, ``dtype``, as
+    many elements as ``shape`` says, on the device of ``ref``."""
+    _on(t, ref, what)
+    _is(t, dtype, what)
+    n = 1
+    for d in shape:
+        n *= d
+    if t.numel() != n or tuple(t.shape[-len(shape):]) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
+def _span(t):
+    """[lo, hi) in bytes of the elements a strided view touches."""
+    lo = t.data_ptr()
+    return lo, lo + (sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+
+
+def _disjoint(x, ld_x, cx, out, ld_out, co, what):
+    """``out`` (``co`` channels of ``ld_out`` per pixel / row) shares no element with the input ``x`` the kernel reads while other
+    workgroups already store: other byte ranges, or two channel intervals of ONE buffer (same ld, same element size) that do not
+    intersect.  Anything else cannot be proven disjoint and is refused."""
+    (xl, xh), (ol, oh) = _span(x), _span(out)
+    if xh <= ol or oh <= xl:
+        return
+    es = x.element_size()
+    d = ol - xl
+    if es == out.element_size() and ld_x == ld_out and d % es == 0:
+        c = (d // es) % ld_x
+        if c >= cx and c + co <= ld_x:
+            return
+    raise ValueError(f"{what}: out shares elements with the input (only a disjoint channel slice of the same buffer may be written)")
 
 
 # ------------------------------------------------------------------------------ weight packing
@@ -176,6 +269,8 @@ def _bias_ptr(pk):
 def conv2d(x, pk, act, residual=None, out=None, out_dtype=None):
     """act(conv(x) + bias) (+ residual) as one implicit-GEMM kernel; see cft_conv2d."""
     _require_cuda(x, "conv2d")
+    _dt(x.dtype)
+    _packed_for(pk, x, "conv2d")
     x, ldx = as_nhwc(x)
     B, C, H, W = x.shape
     if C != pk.cin:
@@ -183,14 +278,17 @@ def conv2d(x, pk, act, residual=None, out=None, out_dtype=None):
     Ho, Wo = conv_out_size(H, W, pk.k, pk.s)
     if out is None:
         out = new_nhwc(B, Ho, Wo, pk.n, out_dtype or x.dtype, x.device)
-    if tuple(out.shape) != (B, pk.n, Ho, Wo):
-        raise ValueError(f"conv2d: out has shape {tuple(out.shape)}, expected {(B, pk.n, Ho, Wo)}")
-    ldy = _view_ld(out, "conv2d out")
+        ldy = pk.n
+    else:
+        if out.dtype != (out_dtype or out.dtype) or out.dtype not in (x.dtype, torch.float32):
+            raise TypeError(f"conv2d: out is {out.dtype}, expected {out_dtype or x.dtype} (the compute dtype or float32)")
+        ldy = _out_view(out, x, "conv2d out", (B, pk.n, Ho, Wo), 8)
+        _disjoint(x, ldx, C, out, ldy, pk.n, "conv2d")
     rp, ldr, rdt = None, 0, CFT_BF16
     if residual is not None:
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError("conv2d: residual shape mismatch")
-        ldr = _view_ld(residual, "conv2d residual")
+        if residual.dtype not in (x.dtype, torch.float32):
+            raise TypeError(f"conv2d: residual is {residual.dtype}, expected the compute dtype {x.dtype} or float32")
+        ldr = _out_view(residual, x, "conv2d residual", out.shape, 8)
         rp, rdt = residual.data_ptr(), _dt(residual.dtype)
     lib = _lib.load()
     es_in, es_out = x.element_size(), out.element_size()
@@ -216,7 +314,7 @@ def conv2d_chain_ok_geometry(B, H, W, dtype, pk1, pk2, ldx=None, ldy=None):
 
 def _chain_geometry(x, pk1):
     """(B, H, W, dtype, ldx) of ``x`` for the ``_geometry`` predicates, or None when ``x`` is not a 4-D GPU tensor of ``pk1.cin`` channels."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.shape[1] == pk1.cin):
+    if not (isinstance(x, torch.Tensor) and _is_cuda(x) and x.dim() == 4 and x.shape[1] == pk1.cin):
         return None
     ldx = x.stride(3) if (x.stride(1) == 1 and x.stride(3) >= x.shape[1]) else None      # (another layout is converted to dense NHWC first)
     return x.shape[0], x.shape[2], x.shape[3], x.dtype, ldx
@@ -232,6 +330,8 @@ def conv2d_chain(x, pk1, pk2, act2, out=None):
     """act2(conv1x1(SiLU(conv(x)))) as ONE kernel (cft_conv2d_chain): the first conv's output tile becomes the second GEMM's A operand
     in LDS.  Bit-identical to ``conv2d(conv2d(x, pk1, ACT_SILU), pk2, act2)``."""
     _require_cuda(x, "conv2d_chain")
+    for pk in (pk1, pk2):
+        _packed_for(pk, x, "conv2d_chain")
     if not conv2d_chain_ok(x, pk1, pk2):
         raise ValueError("conv2d_chain: layer pair not eligible (conv2d_chain_ok)")
     x, ldx = as_nhwc(x)
@@ -239,9 +339,11 @@ def conv2d_chain(x, pk1, pk2, act2, out=None):
     Ho, Wo = conv_out_size(H, W, pk1.k, pk1.s)
     if out is None:
         out = new_nhwc(B, Ho, Wo, pk2.n, x.dtype, x.device)
-    if tuple(out.shape) != (B, pk2.n, Ho, Wo) or out.dtype != x.dtype:
-        raise ValueError(f"conv2d_chain: out has shape {tuple(out.shape)}, expected {(B, pk2.n, Ho, Wo)}")
-    ldy = _view_ld(out, "conv2d_chain out")
+        ldy = pk2.n
+    else:
+        _is(out, x.dtype, "conv2d_chain out")
+        ldy = _out_view(out, x, "conv2d_chain out", (B, pk2.n, Ho, Wo), 8)
+        _disjoint(x, ldx, C, out, ldy, pk2.n, "conv2d_chain")
     lib = _lib.load()
     es = x.element_size()
     M = B * Ho * Wo
@@ -282,21 +384,25 @@ def conv2d_chain_res(x, pk1, res, pk2, act2, out1=None, out2=None):
     and Bottleneck j+1's 1x1 conv inside a C3 with shortcuts.  Bit-identical to ``conv2d(x, pk1, SILU, residual=res)`` followed by
     ``conv2d(y1, pk2, act2)``; y1 is stored but never re-read, and the 1x1 launch disappears."""
     _require_cuda(x, "conv2d_chain_res")
+    for pk in (pk1, pk2):
+        _packed_for(pk, x, "conv2d_chain_res")
     if not conv2d_chain_res_ok(x, pk1, pk2, any_size=True):
         raise ValueError("conv2d_chain_res: layer pair not eligible (conv2d_chain_res_ok)")
     x, ldx = as_nhwc(x)
     B, C, H, W = x.shape
     Ho, Wo = conv_out_size(H, W, pk1.k, pk1.s)
-    if tuple(res.shape) != (B, pk1.n, Ho, Wo) or res.dtype != x.dtype:
-        raise ValueError(f"conv2d_chain_res: residual has shape {tuple(res.shape)}, expected {(B, pk1.n, Ho, Wo)}")
-    ldr = _view_ld(res, "conv2d_chain_res residual")
+    _is(res, x.dtype, "conv2d_chain_res residual")
+    ldr = _out_view(res, x, "conv2d_chain_res residual", (B, pk1.n, Ho, Wo))
     if out1 is None:
         out1 = new_nhwc(B, Ho, Wo, pk1.n, x.dtype, x.device)
     if out2 is None:
         out2 = new_nhwc(B, Ho, Wo, pk2.n, x.dtype, x.device)
-    if tuple(out1.shape) != (B, pk1.n, Ho, Wo) or tuple(out2.shape) != (B, pk2.n, Ho, Wo) or out1.dtype != x.dtype or out2.dtype != x.dtype:
-        raise ValueError("conv2d_chain_res: output shape / dtype mismatch")
-    ldy1, ldy2 = _view_ld(out1, "conv2d_chain_res out1"), _view_ld(out2, "conv2d_chain_res out2")
+    for o in (out1, out2):
+        _is(o, x.dtype, "conv2d_chain_res out")
+    ldy1 = _out_view(out1, x, "conv2d_chain_res out1", (B, pk1.n, Ho, Wo))
+    ldy2 = _out_view(out2, x, "conv2d_chain_res out2", (B, pk2.n, Ho, Wo))
+    _disjoint(x, ldx, C, out1, ldy1, pk1.n, "conv2d_chain_res out1")
+    _disjoint(x, ldx, C, out2, ldy2, pk2.n, "conv2d_chain_res out2")
     lib = _lib.load()
     es = x.element_size()
     M = B * Ho * Wo
@@ -330,13 +436,16 @@ def bottleneck(x, pk1, pk2, shortcut, out=None):
     """x (+) SiLU(conv3x3(SiLU(conv1x1(x)))) for 64 / 128 channels in one kernel (cft_bottleneck); ``out`` must not
     overlap ``x`` (a disjoint channel slice of the same buffer is fine)."""
     _require_cuda(x, "bottleneck")
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"bottleneck: the fused kernel computes in bfloat16 or float16, got {x.dtype}")
+    for pk in (pk1, pk2):
+        _packed_for(pk, x, "bottleneck")
     x, ldx = as_nhwc(x)
     B, C, H, W = x.shape
     if out is None:
         out = new_nhwc(B, H, W, C, x.dtype, x.device)
-    if tuple(out.shape) != (B, C, H, W):
-        raise ValueError(f"bottleneck: out has shape {tuple(out.shape)}, expected {(B, C, H, W)}")
-    ldy = _view_ld(out, "bottleneck out")
+    _is(out, x.dtype, "bottleneck out")
+    ldy = _out_view(out, x, "bottleneck out", (B, C, H, W))
     lib = _lib.load()
     if C == 128 and pk2.w_stages is None:   # one-time: the 3x3 weights as 36 contiguous 8-KiB stage images (cft_bottleneck_pack_w2)
         pk2.w_stages = torch.empty_like(pk2.w)
@@ -357,14 +466,26 @@ def bottleneck(x, pk1, pk2, shortcut, out=None):
 def linear(x, pk, act=ACT_NONE, residual=None, out=None, out_dtype=None):
     """x [rows, K] (row stride >= K) -> [rows, pk.n]; nn.Linear(+bias)(+act)(+residual)."""
     _require_cuda(x, "linear")
+    _dt(x.dtype)
+    _packed_for(pk, x, "linear")
+    ldx = _rows_ld(x, x, "linear input")
     rows, K = x.shape
-    if K != pk.cin or x.stride(1) != 1:
+    if K != pk.cin:
         raise ValueError(f"linear: input [{rows},{K}] does not match packed weight (cin {pk.cin})")
     if out is None:
         out = torch.empty((rows, pk.n), dtype=out_dtype or x.dtype, device=x.device)
+        ldy = pk.n
+    else:
+        if out.dtype != (out_dtype or out.dtype) or out.dtype not in (x.dtype, torch.float32):
+            raise TypeError(f"linear: out is {out.dtype}, expected {out_dtype or x.dtype} (the compute dtype or float32)")
+        ldy = _rows_ld(out, x, "linear out", (rows, pk.n), 8)
+        _disjoint(x, ldx, K, out, ldy, pk.n, "linear")
     rp, ldr, rdt = None, 0, CFT_BF16
     if residual is not None:
-        rp, ldr, rdt = residual.data_ptr(), residual.stride(0), _dt(residual.dtype)
+        if residual.dtype not in (x.dtype, torch.float32):
+            raise TypeError(f"linear: residual is {residual.dtype}, expected the compute dtype {x.dtype} or float32")
+        ldr = _rows_ld(residual, x, "linear residual", (rows, pk.n), 8)
+        rp, rdt = residual.data_ptr(), _dt(residual.dtype)
     lib = _lib.load()
     abytes = (rows * K * x.element_size() + rows * pk.n_valid * out.element_size() + pk.w.numel() * x.element_size()
               + (0 if residual is None else rows * pk.n_valid * residual.element_size()))
@@ -408,9 +529,14 @@ def linear_splitk(x, pk, splits):
     """fp32 partial sums [splits, rows, pk.n] of ``x @ w.T (+ bias)`` over ``splits`` slices of K (cft_linear_splitk); summed in order they equal
     ``linear(x, pk, out_dtype=float32)`` up to fp32 rounding.  ``layernorm_reduce`` folds them into the residual stream."""
     _require_cuda(x, "linear_splitk")
+    _dt(x.dtype)
+    _packed_for(pk, x, "linear_splitk")
+    _rows_ld(x, x, "linear_splitk input")
     rows, K = x.shape
-    if K != pk.cin or x.stride(1) != 1:
+    if K != pk.cin:
         raise ValueError(f"linear_splitk: input [{rows},{K}] does not match packed weight (cin {pk.cin})")
+    if not 2 <= int(splits) <= 8:
+        raise ValueError(f"linear_splitk: splits must be 2 .. 8, got {splits}")
     parts = torch.empty((splits, rows, pk.n), dtype=torch.float32, device=x.device)
     lib = _lib.load()
     abytes = rows * K * x.element_size() + splits * rows * pk.n_valid * 4 + pk.w.numel() * x.element_size()
@@ -424,7 +550,15 @@ def linear_splitk(x, pk, splits):
 def layernorm_reduce(x, parts, gamma, beta, out_dtype, eps=1e-5):
     """x (float32 [rows, C], IN PLACE) += parts[0] + parts[1] + ... (float32 [n, rows, C]); returns LayerNorm(x) in ``out_dtype``."""
     _require_cuda(x, "layernorm_reduce")
+    _on(parts, x, "layernorm_reduce parts")
+    _is(x, torch.float32, "layernorm_reduce x")
+    _is(parts, torch.float32, "layernorm_reduce parts")
+    _dt(out_dtype)
+    if x.dim() != 2 or parts.dim() != 3 or x.data_ptr() % 16 or parts.data_ptr() % 16:
+        raise ValueError(f"layernorm_reduce: x {tuple(x.shape)} / parts {tuple(parts.shape)} must be 16-byte aligned [rows, C] / [n, rows, C] tensors")
     rows, C = x.shape
+    _vec(gamma, x, (C,), "layernorm_reduce gamma")
+    _vec(beta, x, (C,), "layernorm_reduce beta")
     if parts.dtype != torch.float32 or tuple(parts.shape[1:]) != (rows, C) or not parts.is_contiguous() or not x.is_contiguous() or x.dtype != torch.float32:
         raise ValueError(f"layernorm_reduce: x {tuple(x.shape)} {x.dtype} / parts {tuple(parts.shape)} {parts.dtype} must be contiguous fp32 with matching rows")
     out = torch.empty((rows, C), dtype=out_dtype, device=x.device)
@@ -439,20 +573,23 @@ def layernorm_reduce(x, parts, gamma, beta, out_dtype, eps=1e-5):
 def focus_s2d(img, dtype):
     """[B,3,H,W] float image batch (NCHW) -> [B,16,H/2,W/2] NHWC in ``dtype`` (12 real channels)."""
     _require_cuda(img, "focus_s2d")
+    _dt(dtype)
+    if img.dim() != 4:
+        raise ValueError(f"focus_s2d: expected a [B,3,H,W] image batch, got {tuple(img.shape)}")
     if img.dtype == torch.uint8:
         # raw camera bytes, e.g. ``img6[:, :3]`` / ``img6[:, 3:]`` of the reference's [B,6,H,W] uint8 batch:
         # normalisation (/255), channel split (strides) and cast are fused into the gather
         B, C, H, W = img.shape
-        if C != 3 or img.stride(3) != 1:
-            raise ValueError("focus_s2d: uint8 input must be [B,3,H,W] with contiguous rows")
+        if C != 3 or img.stride(3) != 1 or H % 2 or W % 2:
+            raise ValueError("focus_s2d: uint8 input must be [B,3,H,W] with contiguous rows and even H and W")
         out = new_nhwc(B, H // 2, W // 2, 16, dtype, img.device)
         st = _lib.load().cft_focus_s2d_u8(img.data_ptr(), img.stride(0), img.stride(1), img.stride(2), out.data_ptr(),
                                           B, H, W, 1.0 / 255.0, _dt(dtype), _stream())
         _lib.check(st, "cft_focus_s2d_u8")
         return out
     B, C, H, W = img.shape
-    if C != 3:
-        raise ValueError(f"focus_s2d: expected 3 input channels, got {C}")
+    if C != 3 or H % 2 or W % 2:
+        raise ValueError(f"focus_s2d: expected 3 input channels and even H and W, got {tuple(img.shape)}")
     if img.dtype != torch.float32 or not img.is_contiguous():
         # half / bf16 / strided images -> contiguous fp32 NCHW with the conversion kernel: seen as an "NHWC" problem
         # with (batch*channel, row, 1 pixel, W "channels") the output is exactly the contiguous NCHW image
@@ -486,6 +623,8 @@ def focus_conv(img, pk, act, dtype):
     _require_cuda(img, "focus_conv")
     if img.dim() != 4 or img.shape[1] != 3:
         raise ValueError(f"focus_conv: expected a [B,3,H,W] image batch, got {tuple(img.shape)}")
+    _dt(dtype)
+    _packed_for(pk, img, "focus_conv", dtype)
     fusable = (dtype in (torch.bfloat16, torch.float16) and pk.k == 3 and pk.s == 1 and pk.cin == 16 and pk.kpad == 192
                and pk.n in (32, 48, 64, 80) and act in (ACT_NONE, ACT_SILU)
                and (img.dtype in (torch.uint8, torch.float32) or (img.dtype == torch.float16 and dtype == torch.float16)))
@@ -515,8 +654,10 @@ def focus_conv(img, pk, act, dtype):
 def spp_maxpool(buf, C, ks):
     """In-place: buf [B,4C,H,W] NHWC, channels [0,C) already hold x; fills the three pooled slices."""
     _require_cuda(buf, "spp_maxpool")
+    if buf.dim() != 4 or buf.shape[1] != 4 * C:
+        raise ValueError(f"spp_maxpool: buf must be [B, {4 * C}, H, W] (x and its three pooled slices), got {tuple(buf.shape)}")
     B, C4, H, W = buf.shape
-    ld = _view_ld(buf, "spp_maxpool")
+    ld = _out_view(buf, buf, "spp_maxpool")
     st = _lib.load().cft_spp_maxpool(buf.data_ptr(), B, H, W, C, ld, ks[0], ks[1], ks[2], _dt(buf.dtype), _stream())
     _lib.check(st, "cft_spp_maxpool")
     return buf
@@ -525,8 +666,9 @@ def spp_maxpool(buf, C, ks):
 def copy_channels(src, dst, up=0):
     """dst[b, :, y, x] = src[b, :, y >> up, x >> up] (dst is usually a channel slice of a concat buffer)."""
     _require_cuda(src, "copy_channels")
+    _is(dst, src.dtype, "copy_channels dst")
     src, ldi = as_nhwc(src)
-    ldo = _view_ld(dst, "copy_channels dst")
+    ldo = _out_view(dst, src, "copy_channels dst")
     B, C, Ho, Wo = dst.shape
     if src.shape[0] != B or src.shape[1] != C or (src.shape[2] << up) != Ho or (src.shape[3] << up) != Wo:
         raise ValueError(f"copy_channels: {tuple(src.shape)} -> {tuple(dst.shape)} with up={up}")
@@ -537,14 +679,20 @@ def copy_channels(src, dst, up=0):
 
 def add(a, b, out=None):
     _require_cuda(a, "add")
+    _on(b, a, "add b")
+    _dt(a.dtype)
+    _is(b, a.dtype, "add b")
+    if a.shape != b.shape:
+        raise ValueError(f"add: {tuple(a.shape)}/{a.dtype} vs {tuple(b.shape)}/{b.dtype}")
     a, lda = as_nhwc(a)
     b, ldb = as_nhwc(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        raise ValueError(f"add: {tuple(a.shape)}/{a.dtype} vs {tuple(b.shape)}/{b.dtype}")
     B, C, H, W = a.shape
     if out is None:
         out = new_nhwc(B, H, W, C, a.dtype, a.device)
-    ldo = _view_ld(out, "add out")
+        ldo = C
+    else:
+        _is(out, a.dtype, "add out")
+        ldo = _out_view(out, a, "add out", (B, C, H, W))
     st = _lib.load().cft_add(a.data_ptr(), lda, 0, b.data_ptr(), ldb, 0, out.data_ptr(), ldo, 0, B * H * W, C, _dt(a.dtype), _stream())
     _lib.check(st, "cft_add")
     return out
@@ -580,10 +728,16 @@ def gpt_tokenize(rgb, ir, pos_emb, grid=ANCHOR_GRID):
     """-> float32 tokens [B, 2*va*ha, C] (adaptive average pool of both streams to the ``grid`` = (va, ha) anchors, + pos_emb)."""
     _require_cuda(rgb, "gpt_tokenize")
     va, ha = _grid(grid)
+    _on(ir, rgb, "gpt_tokenize ir")
+    _dt(rgb.dtype)
+    _is(ir, rgb.dtype, "gpt_tokenize ir")
+    if rgb.dim() != 4 or ir.shape != rgb.shape:
+        raise ValueError(f"gpt_tokenize: the two streams must be [B,C,H,W] tensors of one shape, got {tuple(rgb.shape)} and {tuple(ir.shape)}")
+    T = 2 * va * ha
+    _vec(pos_emb, rgb, (T, rgb.shape[1]), "gpt_tokenize pos_emb")
     rgb, ld_r = as_nhwc(rgb)
     ir, ld_i = as_nhwc(ir)
     B, C, H, W = rgb.shape
-    T = 2 * va * ha
     tokens = torch.empty((B, T, C), dtype=torch.float32, device=rgb.device)
     lib = _lib.load()
     fn, label, grid_args = _grid_entry(lib, "cft_gpt_tokenize", va, ha)
@@ -597,7 +751,13 @@ def gpt_tokenize(rgb, ir, pos_emb, grid=ANCHOR_GRID):
 def layernorm(x, gamma, beta, out_dtype, eps=1e-5):
     """x float32 [rows, C] -> out_dtype [rows, C]."""
     _require_cuda(x, "layernorm")
+    _is(x, torch.float32, "layernorm x")
+    _dt(out_dtype)
+    if x.dim() != 2 or not x.is_contiguous() or x.data_ptr() % 16:
+        raise ValueError(f"layernorm: x must be a contiguous, 16-byte aligned [rows, C] tensor, got {tuple(x.shape)} with strides {tuple(x.stride())}")
     rows, C = x.shape
+    _vec(gamma, x, (C,), "layernorm gamma")
+    _vec(beta, x, (C,), "layernorm beta")
     out = torch.empty((rows, C), dtype=out_dtype, device=x.device)
     lib = _lib.load()
     st = _timed("cft_layernorm", 0.0, rows * C * (4.0 + out.element_size()),
@@ -611,6 +771,10 @@ def attention(qkv, B, heads, dk, dkp, pdrop=0.0, T=128, general=False):
     kernel.  T = 128 runs the single-tile kernel (cft_attention), any other T (1 .. 2048) the flash-style one (cft_attention_tokens);
     ``general=True`` forces the latter at T = 128 too."""
     _require_cuda(qkv, "attention")
+    _dt(qkv.dtype)
+    if tuple(qkv.shape) != (B * T, 3 * heads * dkp) or not qkv.is_contiguous() or qkv.data_ptr() % 16 or dkp < dk:
+        raise ValueError(f"attention: qkv must be a contiguous, 16-byte aligned [{B * T}, {3 * heads * dkp}] tensor (B * T rows of q | k | v, "
+                         f"heads x dkp each), got {tuple(qkv.shape)} with strides {tuple(qkv.stride())}")
     out = torch.empty((B * T, heads * dkp), dtype=qkv.dtype, device=qkv.device)
     lib = _lib.load()
     seed = next_dropout_seed() if pdrop > 0 else 0
@@ -633,16 +797,23 @@ def gpt_upsample_add(tokens, s, base, H, W, dtype, grid=None):
     _require_cuda(tokens, "gpt_upsample_add")
     grid = token_grid(tokens, grid)
     va, ha = _grid(grid)
-    if (va, ha) != (8, 8) and not gpt_dual_tokens_ok(tokens, grid):
+    if isinstance(tokens, torch.Tensor) and tokens.dtype != torch.float32:
+        raise TypeError(f"gpt_upsample_add: tokens must be float32, got {tokens.dtype}")
+    if s not in (0, 1):
+        raise ValueError(f"gpt_upsample_add: stream index must be 0 or 1, got {s}")
+    _dt(dtype)
+    if not gpt_dual_tokens_ok(tokens, grid):
         raise ValueError(f"gpt_upsample_add: tokens must be a contiguous, 16-byte aligned fp32 [B, {2 * va * ha}, C] tensor (C % 4 == 0), "
                          f"got {tuple(tokens.shape)} {tokens.dtype}")
     B, T, C = tokens.shape
     out = new_nhwc(B, H, W, C, dtype, tokens.device)
     bp, ldb = None, 0
     if base is not None:
+        _on(base, tokens, "gpt_upsample_add base")
+        _is(base, dtype, "gpt_upsample_add base")
+        if tuple(base.shape) != (B, C, H, W):
+            raise ValueError(f"gpt_upsample_add: base has shape {tuple(base.shape)}, expected {(B, C, H, W)}")
         base, ldb = as_nhwc(base)
-        if tuple(base.shape) != (B, C, H, W) or base.dtype != dtype:
-            raise ValueError("gpt_upsample_add: base shape/dtype mismatch")
         bp = base.data_ptr()
     lib = _lib.load()
     fn, label, grid_args = _grid_entry(lib, "cft_gpt_upsample_add", va, ha)
@@ -656,7 +827,7 @@ def gpt_dual_tokens_ok(tokens, grid=None):
     """What ``cft_gpt_upsample_add2`` (and the ``_grid`` de-tokenisers) hard-code about the token tensor: [B, 2*va*ha, C] (two streams x
     va x ha anchors; 128 at the default 8 x 8), fp32, contiguous, C a multiple of 4 and a 16-byte aligned base (rows are read as float4)."""
     va, ha = (int(g) for g in token_grid(tokens, grid))
-    return (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dim() == 3 and tokens.shape[1] == 2 * va * ha
+    return (isinstance(tokens, torch.Tensor) and _is_cuda(tokens) and tokens.dim() == 3 and tokens.shape[1] == 2 * va * ha
             and tokens.dtype == torch.float32 and tokens.is_contiguous() and tokens.shape[2] % 4 == 0 and tokens.data_ptr() % 16 == 0)
 
 
@@ -667,24 +838,28 @@ def gpt_upsample_add_dual(tokens, base0, base1, H, W, dtype, sum_out=None, want_
     _require_cuda(tokens, "gpt_upsample_add_dual")
     grid = token_grid(tokens, grid)
     va, ha = _grid(grid)
+    if isinstance(tokens, torch.Tensor) and tokens.dtype != torch.float32:
+        raise TypeError(f"gpt_upsample_add_dual: tokens must be float32, got {tokens.dtype}")
+    _dt(dtype)
     if not gpt_dual_tokens_ok(tokens, grid):
         raise ValueError(f"gpt_upsample_add_dual: tokens must be a contiguous, 16-byte aligned fp32 [B, {2 * va * ha}, C] tensor (C % 4 == 0), "
                          f"got {tuple(tokens.shape)} {tokens.dtype}")
     B, T, C = tokens.shape
+    for bse in (base0, base1):
+        _on(bse, tokens, "gpt_upsample_add_dual base")
+        _is(bse, dtype, "gpt_upsample_add_dual base")
+        if tuple(bse.shape) != (B, C, H, W):
+            raise ValueError(f"gpt_upsample_add_dual: base has shape {tuple(bse.shape)}, expected {(B, C, H, W)}")
     base0, ldb0 = as_nhwc(base0)
     base1, ldb1 = as_nhwc(base1)
-    for bse in (base0, base1):
-        if tuple(bse.shape) != (B, C, H, W) or bse.dtype != dtype:
-            raise ValueError("gpt_upsample_add_dual: base shape/dtype mismatch")
     out0 = new_nhwc(B, H, W, C, dtype, tokens.device)
     out1 = new_nhwc(B, H, W, C, dtype, tokens.device)
     sp, lds = None, 0
     if want_sum:
         if sum_out is None:
             sum_out = new_nhwc(B, H, W, C, dtype, tokens.device)
-        if tuple(sum_out.shape) != (B, C, H, W) or sum_out.dtype != dtype:
-            raise ValueError("gpt_upsample_add_dual: sum_out shape/dtype mismatch")
-        lds = _view_ld(sum_out, "gpt_upsample_add_dual sum")
+        _is(sum_out, dtype, "gpt_upsample_add_dual sum_out")
+        lds = _out_view(sum_out, tokens, "gpt_upsample_add_dual sum_out", (B, C, H, W))
         sp = sum_out.data_ptr()
     else:
         sum_out = None
@@ -699,7 +874,20 @@ def gpt_upsample_add_dual(tokens, base0, base1, H, W, dtype, sum_out=None, want_
 
 def detect_decode(logits, raw, pred, anchors_px, na, no, stride, row0):
     """logits [B, ldl, ny, nx] NHWC float32; raw [B,na,ny,nx,no]; pred [B,rows,no] (filled at row0)."""
+    _require_cuda(logits, "detect_decode")
+    for t, what in ((logits, "logits"), (raw, "raw"), (pred, "pred")):
+        _on(t, logits, f"detect_decode {what}")
+        _is(t, torch.float32, f"detect_decode {what}")
+    if logits.dim() != 4:
+        raise ValueError(f"detect_decode: logits must be [B, ldl, ny, nx], got {tuple(logits.shape)}")
     B, ldl, ny, nx = logits.shape
+    if _view_ld(logits, "detect_decode logits") != ldl or ldl < na * no or logits.data_ptr() % 16:
+        raise ValueError(f"detect_decode: logits must be a dense, 16-byte aligned NHWC tensor of >= {na * no} channels")
+    if tuple(raw.shape) != (B, na, ny, nx, no) or not raw.is_contiguous() or raw.data_ptr() % 16 or pred.data_ptr() % 16:
+        raise ValueError(f"detect_decode: raw must be a contiguous {(B, na, ny, nx, no)} tensor, got {tuple(raw.shape)}")
+    if pred.dim() != 3 or pred.shape[0] != B or pred.shape[2] != no or not pred.is_contiguous() or row0 < 0 or row0 + na * ny * nx > pred.shape[1]:
+        raise ValueError(f"detect_decode: pred must be a contiguous [{B}, rows, {no}] tensor with rows >= row0 + {na * ny * nx}, got {tuple(pred.shape)} (row0 {row0})")
+    _vec(anchors_px, logits, (na * 2,), "detect_decode anchors_px")
     st = _lib.load().cft_detect_decode(logits.data_ptr(), ldl, raw.data_ptr(), pred.data_ptr(), anchors_px.data_ptr(),
                                        B, ny, nx, na, no, float(stride), row0, pred.shape[1], _stream())
     _lib.check(st, "cft_detect_decode")
@@ -977,8 +1165,11 @@ def dropout_(x, p):
     _require_cuda(x, "dropout_")
     if p <= 0.0:
         return x
-    if not x.is_contiguous():
-        raise ValueError("dropout_: tensor must be contiguous")
+    _dt(x.dtype)
+    if not x.is_contiguous() or x.data_ptr() % 16 or x.numel() == 0:
+        raise ValueError("dropout_: tensor must be contiguous, 16-byte aligned and not empty")
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"dropout_: p must be in [0, 1), got {p}")
     st = _lib.load().cft_dropout(x.data_ptr(), x.numel(), float(p), next_dropout_seed(), _dt(x.dtype), _stream())
     _lib.check(st, "cft_dropout")
     return x
@@ -986,6 +1177,11 @@ def dropout_(x, p):
 
 def add_rows_(x, y):
     """x += y for two [rows, C] tensors of one dtype (the CFT residual stream in training mode)."""
+    _require_cuda(x, "add_rows_")
+    _dt(x.dtype)
+    _is(y, x.dtype, "add_rows_ y")
+    _rows_ld(x, x, "add_rows_ x")
+    _rows_ld(y, x, "add_rows_ y", x.shape)
     rows, C = x.shape
     st = _lib.load().cft_add(x.data_ptr(), x.stride(0), 0, y.data_ptr(), y.stride(0), 0, x.data_ptr(), x.stride(0), 0, rows, C, _dt(x.dtype), _stream())
     _lib.check(st, "cft_add(rows)")
@@ -996,23 +1192,30 @@ def batchnorm_train(y32, C, bn, act, residual=None, out=None, out_dtype=None):
     """act(BatchNorm2d(y32)) with BATCH statistics (+ residual) and the running-statistics update of ``bn``
     (an nn.BatchNorm2d in training mode): y32 is the fp32 conv output [B, pad8(C), H, W] (NHWC)."""
     _require_cuda(y32, "batchnorm_train")
+    _is(y32, torch.float32, "batchnorm_train input")
+    if y32.dim() != 4 or not 0 < C <= y32.shape[1]:
+        raise ValueError(f"batchnorm_train: input must be [B, pad8({C}), H, W], got {tuple(y32.shape)}")
     B, Cp, H, W = y32.shape
-    ldx = _view_ld(y32, "batchnorm_train input")
-    out_dtype = out_dtype or torch.float32
+    ldx = _out_view(y32, y32, "batchnorm_train input")
     if out is None:
+        out_dtype = out_dtype or torch.float32
         out = new_nhwc(B, H, W, Cp, out_dtype, y32.device)[:, :C] if Cp != C else new_nhwc(B, H, W, C, out_dtype, y32.device)
-    if tuple(out.shape) != (B, C, H, W):
-        raise ValueError(f"batchnorm_train: out has shape {tuple(out.shape)}, expected {(B, C, H, W)}")
-    ldy = _view_ld(out, "batchnorm_train out")
+    elif out_dtype is not None:
+        _is(out, out_dtype, "batchnorm_train out")
+    ldy = _out_view(out, y32, "batchnorm_train out", (B, C, H, W))
+    cp8 = -(-C // 8) * 8         # the kernel stores (and reads the shortcut in) whole granules up to pad8(C): they must lie inside the pixel
+    if out.storage_offset() % ldy + cp8 > ldy:
+        raise ValueError(f"batchnorm_train: out needs room for pad8({C}) = {cp8} channels inside each pixel")
     track = bn.track_running_stats and bn.running_mean is not None
     for t in (bn.weight, bn.bias) + ((bn.running_mean, bn.running_var) if track else ()):     # (no running statistics: track_running_stats=False)
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != y32.device:
-            raise TypeError("batchnorm_train: BatchNorm parameters / running statistics must be contiguous fp32 tensors on the GPU")
+        _vec(t, y32, (C,), "batchnorm_train BatchNorm parameters / running statistics")
     rp, ldr, rdt = None, 0, CFT_F32
     if residual is not None:
-        if tuple(residual.shape) != (B, C, H, W):
-            raise ValueError("batchnorm_train: residual shape mismatch")
-        ldr, rp, rdt = _view_ld(residual, "batchnorm_train residual"), residual.data_ptr(), _dt(residual.dtype)
+        if residual.dtype not in (out.dtype, torch.float32):
+            raise TypeError(f"batchnorm_train: residual is {residual.dtype}, expected the output dtype {out.dtype} or float32")
+        ldr, rp, rdt = _out_view(residual, y32, "batchnorm_train residual", (B, C, H, W)), residual.data_ptr(), _dt(residual.dtype)
+        if residual.storage_offset() % ldr + cp8 > ldr:
+            raise ValueError(f"batchnorm_train: residual needs room for pad8({C}) = {cp8} channels inside each pixel")
     lib = _lib.load()
     M = B * H * W
     ws = torch.empty((lib.cft_batchnorm_train_workspace(M, C),), dtype=torch.uint8, device=y32.device)

@@ -199,6 +199,25 @@ def test_linear_splitk_parts_and_layernorm_reduce(dev, dtype, rows, n, K, splits
     _ln_check(xr[sel].cpu(), gamma.cpu(), beta.cpu(), y[sel].cpu(), dtype, f"layernorm_reduce {rows}x{pk.n} {dtype}")
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+@pytest.mark.parametrize("C", [4, 512, 516, 1280, 1284, 4096])
+def test_layernorm_reduce_every_instantiation(dev, dtype, C):
+    """cft_layernorm_reduce at 5 rows on the widths of LN_SHAPES (three partial sums): the folded stream against the float64 sum of its
+    terms, the LayerNorm of it per element."""
+    from msod_amd import ops
+    rows, nparts = 5, 3
+    x = _rnd(rows, C, seed=81) * 3 + 1
+    parts = _rnd(nparts, rows, C, seed=82)
+    g, b = _rnd(C, seed=83) * 0.2 + 1, _rnd(C, seed=84) * 0.1
+    xr = x.to(dev)
+    y = ops.layernorm_reduce(xr, parts.to(dev), g.to(dev), b.to(dev), dtype)
+    torch.cuda.synchronize()
+    ref = x.double() + parts.double().sum(0)
+    mag = x.double().abs() + parts.double().abs().sum(0)
+    assert ((xr.cpu().double() - ref).abs() <= nparts * X.U24 * mag).all(), "the folded residual stream"
+    _ln_check(xr.cpu(), g, b, y.cpu(), dtype, f"layernorm_reduce {rows}x{C} {dtype}")
+
+
 def _ln_check(x, g, b, y, dtype, what):
     """LayerNorm of fp32 rows x against float64: fp32 mean / variance over C and one output rounding."""
     x64, g64, b64 = x.double(), g.double(), b.double()
@@ -212,8 +231,13 @@ def _ln_check(x, g, b, y, dtype, what):
     return X.assert_close(y.double().numpy(), ref, bound, dtype, FLOOR[dtype], what)
 
 
-@pytest.mark.parametrize("rows", [8192, 300])
-@pytest.mark.parametrize("C", [64, 256, 320, 1024, 1280])
+# layernorm_launch picks one of three instantiations by C / 4 (<= 128, <= 320, else 16 vectors per lane): the 5-row shapes reach all three,
+# the smallest and the largest C the launcher takes, and widths either side of each threshold
+LN_SHAPES = [(rows, C) for rows in (8192, 300) for C in (64, 256, 320, 1024, 1280)] + [(5, C) for C in (4, 512, 516, 1280, 1284, 4096)]
+LN_IDS = [f"{C}-{rows}" for rows, C in LN_SHAPES]
+
+
+@pytest.mark.parametrize("rows,C", LN_SHAPES, ids=LN_IDS)
 def test_layernorm_per_element(dev, rows, C):
     from msod_amd import ops
     x = _rnd(rows, C, seed=22) * 3 + 1

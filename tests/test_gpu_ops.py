@@ -433,8 +433,11 @@ def test_errors_are_loud(dev):
         ops.conv2d(torch.zeros(1, 8, 4, 4, dtype=torch.bfloat16), pk, 0)     # CPU tensor
     with pytest.raises(TypeError):
         ops.conv2d(torch.zeros(1, 8, 4, 4, device=dev, dtype=torch.float64), pk, 0)
+    with pytest.raises(TypeError, match="packed weight"):
+        ops.conv2d(torch.zeros(1, 8, 4, 4, device=dev, dtype=torch.float16), pk, 0)      # fp16 in, weights packed in bf16
+    pk16 = ops.pack_conv(torch.zeros(8, 8, 1, 1), None, torch.float16, device=dev)
     with pytest.raises(RuntimeError, match="compute dtype"):
-        ops.conv2d(torch.zeros(1, 8, 4, 4, device=dev, dtype=torch.float16), pk, 0, out_dtype=torch.bfloat16)   # fp16 in, bf16 out
+        ops.conv2d(torch.zeros(1, 8, 4, 4, device=dev, dtype=torch.float16), pk16, 0, out_dtype=torch.bfloat16)   # fp16 in, bf16 out
 
 
 TILE_VARIANTS = [1, 2, 4, 6, 7, 8, 23, 27, 30, 32, 33, 51, 60, 63, 70, 71, 72, 73, 74, 75]
